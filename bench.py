@@ -28,6 +28,8 @@ PMC child passes made in this run (live_traffic).  The other BASELINE configs ri
 figures with their own roofline fractions: `decode_1gpu` (configs[2]), `fakequant_block` (configs[3]),
 `config5` (configs[4]); `--figure NAME` runs one of them alone.  `cpu_baseline` times the CPU restatement of the
 reference's dequant + F.linear (oracle/cpu_linear.py) on a bounded sample, rank 0 / N = 1 only.
+`--dump-outputs DIR` (N = 1) writes a fixed sample of every Linear's output of the last timed step as DIR/<linear>.npy
+(dump_outputs); weights and inputs are seeded, so two builds given the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -54,6 +56,43 @@ from mxq_amd.pipeline import LayerPipeline, rank_census  # noqa: E402
 
 SEQ = 2048
 PEAK_F16_TFLOPS = 2500.0     # MI355X dense fp16 MFMA (MI355X_MICROARCH.md, chip-level parameters)
+DUMP_SAMPLES = 1 << 15       # --dump-outputs: elements kept per Linear output (7 x 32 Linears x 128 KiB = 28 MiB of float32)
+
+
+def dump_index(M, N, samples=DUMP_SAMPLES):
+    """Flat indices of the --dump-outputs sample of an [M, N] output: one element in each of `samples` equal strides, its
+    offset inside the stride from a fixed 64-bit LCG of the stride number (the same on every machine and library version)."""
+    import numpy as np
+    stride = M * N // samples
+    k = np.arange(samples, dtype=np.uint64)
+    off = ((k * np.uint64(6364136223846793005) + np.uint64(1442695040888963407)) >> np.uint64(33)) % np.uint64(stride)
+    return (k * np.uint64(stride) + off).astype(np.int64)
+
+
+def dump_outputs(out_dir, stage, x_h, buffers, dev):
+    """--dump-outputs DIR (N = 1): what the timed step computed, as DIR/<linear>.npy float32 [layers, DUMP_SAMPLES] --
+    row l holds layer l's output of that Linear at the flat indices dump_index(tokens, out_features).  Every Linear's
+    output buffer is overwritten within a step, so the step is run once more after the timed region with a sampling hook
+    (the timed steps stay untouched), and the buffers it ends with must equal, bit for bit, those the last timed step
+    left behind: the files are the timed step's outputs, not merely a step like it."""
+    import numpy as np
+    last = [b.clone() for b in buffers]
+    idx, got = {}, {}
+
+    def sample(name, y):
+        key = tuple(y.shape)
+        if key not in idx:
+            idx[key] = torch.from_numpy(dump_index(*key)).to(dev)
+        got.setdefault(name, []).append(y.view(-1).index_select(0, idx[key]))
+    stage(x_h, after=sample)
+    torch.cuda.synchronize()
+    packing.workspace_status(dev)
+    if not all(torch.equal(a, b) for a, b in zip(last, buffers)):
+        raise SystemExit("bench.py --dump-outputs: the replayed step differs from the last timed step")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, rows in got.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), torch.stack(rows).float().cpu().numpy())
+    print(f"bench.py: wrote {len(got)} arrays of the last timed step to {out_dir}", file=sys.stderr, flush=True)
 
 
 def build_layers(layers, dev):
@@ -440,13 +479,20 @@ def main():
     ap.add_argument("--path", default="auto",
                     help="packing.linear path of the timed launches.  Default 'auto' = the product entry, mxq_linear_f16_auto, with "
                          "the workspace and scratch QuantLinear.forward passes; 'gemm', 'whole', 'gemm8', ... pick one schedule (A/B)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps, write what the last one computed -- a fixed sample of every Linear's output, "
+                         "DIR/<linear>.npy float32 [layers, samples] -- so that two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus and world > 1:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
+    if args.dump_outputs and (world > 1 or args.figure):
+        raise SystemExit("--dump-outputs dumps the headline step of a single-GPU run (not with --gpus > 1 or --figure)")
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a ROCm GPU (there is no CPU fallback for the measured path)")
     # (MXQ_BENCH_BACKEND=gloo rehearses the N > 1 control flow on a box with fewer GPUs than ranks: ranks then
@@ -496,13 +542,15 @@ def main():
     recv_buf = torch.empty_like(x_h)
     n_micro = world          # sequences in flight per step: per-GPU work stays one full-model pass
 
-    def stage(x_hidden):
+    def stage(x_hidden, after=None):
         # every launch goes through packing.linear(path="auto") -> mxq_linear_f16_auto: the entry QuantLinear.forward calls,
         # with the per-stream workspace it passes (2048 tokens: the 256-token fused kernel, stream-K tail on gate / up)
         for lin in layers:
             for name, p in lin:
                 x = x_i if p.K == LS.INTERMEDIATE else x_hidden
-                packing.linear(x, p, out=(y_f[p.N] if p.N in y_f else y_i if p.N == LS.INTERMEDIATE else y_h), path=args.path)
+                y = packing.linear(x, p, out=(y_f[p.N] if p.N in y_f else y_i if p.N == LS.INTERMEDIATE else y_h), path=args.path)
+                if after is not None:      # --dump-outputs only, after the timed region
+                    after(name, y)
 
     # N > 1: the schedule is mxq_amd.pipeline.LayerPipeline's (the same object the gloo tests drive on CPU): irecv of
     # micro-batch b+1 posted before b is computed, isend of b's output from a ring slot under b+1's compute
@@ -572,6 +620,8 @@ def main():
         if world == 1:
             raise
         ws_status = str(e)
+    if args.dump_outputs:      # before the side figures, which reuse y_h
+        dump_outputs(args.dump_outputs, stage, x_h, [y_h, y_i, *y_f.values()], dev)
     sclk = clocks.mhz()
     bits_per_weight = sum(p.nbytes() for lin in layers for _, p in lin) * 8.0 / (LS.PARAMS_PER_LAYER * max(1, len(my_layers)))
     tokens_per_step = SEQ * n_micro

@@ -20,6 +20,9 @@ Reference entry points exercised:
   G7 act         models.utils_quant.SymQuantizer / AsymQuantizer fwd/bwd (2-D, 3-D, 4-D).
   G8 uniform     lib.quantizer.Quantizer as uniform W2 (group 16) / W4 (per row) quantiser.
   G9 act16       SymQuantizer / AsymQuantizer forward on bf16 / fp16 tensors (uint16 bit patterns).
+  G10 modeling   what models.modeling_llama_quant takes from models.utils_quant: the names it
+                 imports, every QuantizeLinear(...) call of LlamaDecoderLayer (arguments as JSON),
+                 the quantiser classes it stores, and the layer's state_dict keys / shapes.
 
     python tests/golden/make_golden.py g9        # regenerate selected sets only
 """
@@ -329,11 +332,45 @@ def g9_act_quantizers_16bit():
     np.savez_compressed(os.path.join(OUT, "g9_act16.npz"), **out)
 
 
+def g10_modeling_surface():
+    """The reference's decoder layer built once with a recording QuantizeLinear: the calls, imports and quantiser
+    attributes it makes of utils_quant, stored as JSON so that tests replay them against mxq_amd.utils_quant."""
+    import json
+    import models.modeling_llama_quant as M
+    import models.utils_quant as UQ
+    from models.configuration_llama import LlamaConfig
+    calls = []
+
+    class Recording(UQ.QuantizeLinear):
+        def __init__(self, *args, **kwargs):
+            calls.append((self, list(args), dict(kwargs)))
+            super().__init__(*args, **kwargs)
+
+    cfg = LlamaConfig(hidden_size=256, intermediate_size=704, num_attention_heads=4, num_hidden_layers=1, vocab_size=128)
+    cfg.w_bits, cfg.a_bits, cfg.kv_bits = 2, 16, 16      # train.py:56-58
+    saved = M.QuantizeLinear
+    M.QuantizeLinear = Recording
+    try:
+        layer = M.LlamaDecoderLayer(cfg)
+    finally:
+        M.QuantizeLinear = saved
+    names = {id(m): n for n, m in layer.named_modules()}
+    quantizers = {n: {a: v.__name__ for a, v in vars(m).items() if isinstance(v, type) and getattr(UQ, v.__name__, None) is v}
+                  for n, m in layer.named_modules()}
+    surface = {
+        "imports": sorted(n for n, v in vars(M).items() if getattr(UQ, n, None) is v and getattr(v, "__module__", "") == UQ.__name__),
+        "calls": [{"module": names[id(m)], "args": a, "kwargs": k} for m, a, k in calls],
+        "quantizer_attrs": {n: q for n, q in quantizers.items() if q},
+        "state_dict": {k: list(v.shape) for k, v in layer.state_dict().items()},
+    }
+    np.savez_compressed(os.path.join(OUT, "g10_modeling_surface.npz"), surface_json=np.array(json.dumps(surface, sort_keys=True)))
+
+
 if __name__ == "__main__":
     torch.set_num_threads(8)
     gens = [("g1", g1_ptq_small), ("g2", g2_ptq_slices), ("g3", g3_qat_small), ("g4", g4_qlinear),
             ("g5", g5_block_small), ("g6", g6_kat), ("g7", g7_act_quantizers), ("g8", g8_uniform),
-            ("g9", g9_act_quantizers_16bit)]
+            ("g9", g9_act_quantizers_16bit), ("g10", g10_modeling_surface)]
     want = set(a.lower() for a in sys.argv[1:])
     for name, fn in gens:
         if not want or name in want:
