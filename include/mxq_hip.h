@@ -87,14 +87,13 @@ int mxq_dequant_f16(const void* qweight, const void* rowmeta, void* w16, int N, 
  * The fused unpack + per-group scale/zero + W2/4 x A16 product behind a quantised
  * nn.Linear.  Counterpart of gemm_forward_cuda (gemm_cuda.h:3-4, MFMA path, any M) and of
  * gemv_mxq_forward_cuda (gemv_mxq_cuda.h:4-12, streaming path, chosen for M <= 4).
- * Without a workspace the K range is never split: streaming GEMV (M <= 4), skinny MFMA kernel (<= 64), mid-M kernel
- * with one slice per tile (<= 256), prefill kernel with whole tiles beyond; mxq_linear_f16_ws is the fast entry for
+ * The workspace-free schedule of the dispatch (enum mxq_linear_sched below); mxq_linear_f16_ws is the fast entry for
  * 20 < M <= 1024.  x, y, qweight must be 16-byte aligned; y must not alias x. */
 int mxq_linear_f16(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
                    void* stream);
 /* The code paths of mxq_linear_f16, exposed for benchmarking / testing: streaming GEMV (M <= 4), skinny MFMA kernel
- * (5..40 tokens in the dispatch: every packed byte read once, a lane dequantises the MFMA operand it owns; the reference
- * re-reads the weights once per batch row, gemv_mxq_cuda.cu:261-262), prefill GEMM.  mxq_skinny_f16 accepts 1 <= M <= 64
+ * (every packed byte read once, a lane dequantises the MFMA operand it owns; the reference re-reads the weights once per
+ * batch row, gemv_mxq_cuda.cu:261-262), prefill GEMM.  mxq_skinny_f16 accepts 1 <= M <= 64
  * and any layout (MXQ_LAYOUT_*, below: mixed with exact or compact metadata, W2G16, W4ROW). */
 int mxq_skinny_f16(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K, int layout,
                    void* stream);
@@ -108,14 +107,9 @@ int mxq_gemv_f16(const void* x, const void* qweight, const void* rowmeta, void* 
  * `workspace` is device memory of at least mxq_gemm_workspace_bytes() bytes, 16-byte aligned, whose
  * first 64 KiB the caller zeroes ONCE (hipMemset) before first use; the kernels leave it zeroed, so
  * it can be reused by every later launch on the SAME stream (launches on different streams need
- * different workspaces).  workspace == NULL selects the workspace-free schedule of mxq_linear_f16; a workspace too small
- * for the mid-M kernel's partial tiles hands 41..256 tokens to the prefill kernel.
- * The tail is only split where that pays (about 20 idle K-steps per CU: for 256 < M <= 1024 on the Llama shapes and for
- * gate/up at M = 2048).  Beyond 64 tokens, launches of up to 176 tiles of 128 x 128 run the same kernel built with a
- * 128-token tile (csrc/gemm8h.hip; csrc/gemm8n.hip, a 128 x 64 tile, where K <= 6144): up to 64 tiles (e.g. 4096^2 at 65-256
- * tokens) with K cut into one slice per idle CU, fp32 slabs in the workspace beyond its first 64 KiB and a combine launch; 65..176 tiles (gate/up at 65-256 tokens, 4096^2 at
- * 257-640) in one launch, stream-K over the otherwise idle CUs.  Up to 64 tokens, launches of 65..176 tiles of 64 x 128
- * (gate/up) run its 64-token build (csrc/gemm8q.hip) the same way.
+ * different workspaces).  workspace == NULL (or 0 bytes) selects the workspace-free schedule of mxq_linear_f16.  The
+ * schedule by token count, tile count and workspace: enum mxq_linear_sched below.  The prefill kernel splits its tail only
+ * where that pays (about 20 idle K-steps per CU: for 256 < M <= 1024 on the Llama shapes and for gate/up at M = 2048).
  * mxq_gemm_f16_ws runs ONE named schedule (enum mxq_gemm_variant below) at any token count: the entry behind the parity
  * tests of every kernel build and behind tools/'s A/B timings; production callers use mxq_linear_f16_auto.  Results of every
  * variant agree to fp32-summation-order rounding and are run-to-run deterministic; an unknown code is MXQ_E_SHAPE.
@@ -150,8 +144,40 @@ int mxq_workspace_status(const void* workspace, size_t workspace_bytes, int* sta
  * as 4 x uint64 each into `out32_u64` (32 x uint64, device memory).  Two stamps on one stream around a timed region give the
  * shader clock the chip held in between, d(s_memtime) / d(s_memrealtime) x 100 MHz per XCD (bench.py: roofline.sclk_MHz). */
 int mxq_clock_stamp(void* out32_u64, void* stream);
-/* Bytes of workspace the dispatch of mxq_linear_f16_auto can use for a call of this shape (0: it never touches one --
- * GEMV, skinny kernel, or, with `hoisting` != 0, the hoisted mode from mxq_hoist_min_tokens() tokens on); at most
+/* The quantised Linear's dispatch: ONE rule (csrc/capi.hip plan_linear, where each measured threshold and its profile
+ * live) behind mxq_linear_f16, mxq_linear_f16_ws, mxq_linear_f16_layout_ws, mxq_linear_f16_auto and
+ * mxq_linear_workspace_need.  mxq_linear_schedule returns the schedule a call of this shape runs with a workspace of
+ * `workspace_bytes` and a hoisting scratch of `scratch_bytes` (0: none), or MXQ_E_SHAPE.  Host-only, no device work.
+ *   - from mxq_hoist_min_tokens() (4096) tokens, given a scratch of mxq_hoist_scratch_bytes(N, K): HOISTED;
+ *   - M <= 4: GEMV;
+ *   - no workspace (the K range is never split): SKINNY up to 64 tokens (uniform layouts 48); then, mixed layouts up to
+ *     256 tokens, MIDM with one slice per tile; beyond, TILE128 (exact metadata, <= 128 tokens) or FUSED256, whole tiles;
+ *   - with a workspace: SKINNY up to 40 tokens, 20 for weights of more than 24 M elements (uniform layouts 48).  Then by
+ *     tile count -- up to 64 tokens on 64 x 128 tiles: 65..176 of them FUSED64_STREAMK, <= 64 FUSED64_SLICES (uniform
+ *     layouts; the mixed ones go on to MIDM); beyond 64 tokens on 128 x 128 tiles: 65..176 FUSED128_STREAMK, <= 64
+ *     FUSED128_SLICES, or where K <= 6144 the 128 x 64 tile (FUSED128N64_SLICES up to 64 such tiles, _STREAMK beyond).
+ *     Otherwise, mixed layouts up to 256 tokens, MIDM when the workspace holds two partial tiles per output tile; FUSED256
+ *     (stream-K tail where it pays) beyond.
+ *   MIDM is skipped where its 32-bit offsets do not hold the weight.  SLICES: every tile's K range cut into one slice per
+ *   idle CU, fp32 partial tiles in the workspace beyond its 64-KiB head, a combine launch; STREAMK: one launch, stream-K
+ *   over the otherwise idle CUs. */
+enum mxq_linear_sched {
+    MXQ_SCHED_GEMV = 1,                  /* streaming GEMV (csrc/gemv.hip) */
+    MXQ_SCHED_SKINNY = 2,                /* skinny MFMA kernel (csrc/skinny.hip) */
+    MXQ_SCHED_MIDM = 3,                  /* mid-M split-K kernel (csrc/midm.hip) */
+    MXQ_SCHED_FUSED64_STREAMK = 4,       /* the fused kernel's 64-token build (csrc/gemm8q.hip) */
+    MXQ_SCHED_FUSED64_SLICES = 5,
+    MXQ_SCHED_FUSED128_STREAMK = 6,      /* ... its 128-token build (csrc/gemm8h.hip) */
+    MXQ_SCHED_FUSED128_SLICES = 7,
+    MXQ_SCHED_FUSED128N64_STREAMK = 8,   /* ... its 128 x 64-tile build (csrc/gemm8n.hip) */
+    MXQ_SCHED_FUSED128N64_SLICES = 9,
+    MXQ_SCHED_FUSED256 = 10,             /* the 256 x 128-tile fused kernel (csrc/gemm8.hip) */
+    MXQ_SCHED_TILE128 = 11,              /* the 128 x 128-tile kernel (csrc/gemm.hip) */
+    MXQ_SCHED_HOISTED = 12               /* hoisted-dequant mode (mxq_linear_f16_hoisted) */
+};
+int mxq_linear_schedule(int M, int N, int K, int layout, size_t workspace_bytes, size_t scratch_bytes);
+/* Bytes of workspace the dispatch uses for a call of this shape given a full workspace (and, with `hoisting` != 0, a full
+ * scratch): with that many it picks the same schedule; 0 where it touches none (GEMV, SKINNY, HOISTED); at most
  * mxq_gemm_workspace_bytes().  For callers that own one workspace per captured graph.  Host-only helper. */
 size_t mxq_linear_workspace_need(int M, int N, int K, int layout, int hoisting);
 /* hipStreamGetCaptureInfo through this library's HIP runtime: *active = 1 and *id = the capture sequence's id while
@@ -161,17 +187,10 @@ int mxq_linear_f16_ws(const void* x, const void* qweight, const void* rowmeta, v
                       void* workspace, size_t workspace_bytes, void* stream);
 int mxq_gemm_f16_ws(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
                     int variant, void* workspace, size_t workspace_bytes, void* stream);
-/* mxq_linear_f16_ws for a weight in any layout (MXQ_LAYOUT_*: mixed with exact or compact metadata, W2G16, W4ROW).
- * Dispatch by token count: <= 4 the streaming GEMV, then the skinny MFMA kernel (mixed layouts: up to 40 tokens, 20 for
- * weights of more than 24 M elements, where its time has overtaken the split-K kernel's; uniform layouts: up to 48, where
- * the prefill kernel takes over), beyond 64 tokens launches of up to 176 tiles of 128 x 128 the fused kernel's 128-token
- * build (every layout; slices mode up to 64 tiles, stream-K mode beyond), and otherwise up to 256 tokens the mid-M split-K
- * kernel (csrc/midm.hip: K cut into slices over the workgroups, fp32 partial tiles in the workspace beyond its first
- * 64 KiB, summed in slice order by a second launch -- the reference launcher's split_k_iters regime,
- * gemm_cuda_gen.cu:429-475) for the mixed layouts, the prefill kernel otherwise.  The mid-M kernel does not touch
- * the workspace's counters.  workspace == NULL: ONE workspace-free schedule for every layout -- GEMV (<= 4 tokens), the skinny
- * kernel (mixed layouts <= 64, uniform <= 48), the mid-M kernel unsplit (mixed layouts, <= 256), whole tiles of the prefill
- * kernel beyond (csrc/capi.hip linear_noworkspace). */
+/* mxq_linear_f16_ws for a weight in any layout (MXQ_LAYOUT_*: mixed with exact or compact metadata, W2G16, W4ROW), same
+ * dispatch (enum mxq_linear_sched).  The mid-M split-K kernel (csrc/midm.hip: K cut into slices over the workgroups, fp32
+ * partial tiles in the workspace beyond its first 64 KiB, summed in slice order by a second launch -- the reference
+ * launcher's split_k_iters regime, gemm_cuda_gen.cu:429-475) does not touch the workspace's counters. */
 int mxq_linear_f16_layout_ws(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
                              int layout, void* workspace, size_t workspace_bytes, void* stream);
 
@@ -185,11 +204,10 @@ size_t mxq_hoist_scratch_bytes(int N, int K);
 int mxq_linear_f16_hoisted(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
                            int layout, void* w16_scratch, size_t scratch_bytes, void* stream);
 
-/* ONE call for the whole dispatch -- the counterpart of the reference's single entry, whose launcher picks its schedule
- * inside (gemm_cuda.h:3-4, gemm_cuda_gen.cu:424-478: tile kernel by OC, split_k_iters): streaming GEMV, skinny MFMA kernel,
- * mid-M split-K kernel, fused prefill GEMM with its stream-K tail (mxq_linear_f16_layout_ws with `workspace`, which may
- * be NULL), and -- from mxq_hoist_min_tokens() tokens on, when `w16_scratch` holds mxq_hoist_scratch_bytes(N, K) bytes --
- * the hoisted-dequant mode above.  A NULL or too small scratch never fails: the fused kernel runs instead. */
+/* ONE call for the whole dispatch (enum mxq_linear_sched) -- the counterpart of the reference's single entry, whose
+ * launcher picks its schedule inside (gemm_cuda.h:3-4, gemm_cuda_gen.cu:424-478: tile kernel by OC, split_k_iters):
+ * mxq_linear_f16_layout_ws with `workspace` (which may be NULL), plus the hoisted-dequant mode above when `w16_scratch`
+ * holds mxq_hoist_scratch_bytes(N, K) bytes.  A NULL or too small scratch never fails: the fused kernel runs instead. */
 int mxq_hoist_min_tokens(void);
 int mxq_linear_f16_auto(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K, int layout,
                         void* workspace, size_t workspace_bytes, void* w16_scratch, size_t scratch_bytes, void* stream);

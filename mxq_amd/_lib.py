@@ -15,6 +15,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmxq_hip.so")
 
 DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2
+# mxq_linear_schedule's result: include/mxq_hip.h enum mxq_linear_sched
+SCHED_NAMES = {1: "gemv", 2: "skinny", 3: "midm", 4: "fused64_streamk", 5: "fused64_slices", 6: "fused128_streamk",
+               7: "fused128_slices", 8: "fused128n64_streamk", 9: "fused128n64_slices", 10: "fused256", 11: "tile128",
+               12: "hoisted"}
 
 _ERRORS = {-1: "invalid shape (need N % 16 == 0, K % 64 == 0, positive sizes, supported group size)",
            -2: "null pointer", -3: "unknown dtype code", -4: "pointer not 16-byte aligned"}
@@ -46,6 +50,7 @@ SIGNATURES = {
     "mxq_workspace_status": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),
     "mxq_clock_stamp": (c_int, [c_void_p, c_void_p]),
     "mxq_linear_workspace_need": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "mxq_linear_schedule": (c_int, [c_int, c_int, c_int, c_int, c_size_t, c_size_t]),
     "mxq_stream_capture_id": (c_int, [c_void_p, c_void_p, c_void_p]),
     "mxq_hoist_scratch_bytes": (c_size_t, [c_int, c_int]),
     "mxq_linear_f16_hoisted": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),

@@ -295,20 +295,28 @@ int mxq_dense_f16(const void* x, const void* w16, void* y, int M, int N, int K, 
     return dense_f16(x, w16, y, M, N, K, variant, (hipStream_t)stream);
 }
 
-// Token counts the mid-M split-K kernel (midm.hip) may serve: above the skinny kernel's range, below the point where the
-// prefill kernel's 256 x 128 tiles win again (profiles/r03_midM.txt).  Since round 4 the fused kernel's 128- / 64-token builds
-// (gemm8h_mode / gemm8q_mode below) take most of that range when a full workspace is given: what is left to this kernel is
-// 21 / 41 .. 64 tokens on launches of <= 64 tiles (and up to 256 tokens where the workspace is too small for those builds,
-// or absent).  The whole map against hipBLASLt: profiles/r04_dispatch_map.txt.
-static const int MIDM_MAX_TOKENS = 256;
+// ---- the quantised Linear: ONE dispatch rule (include/mxq_hip.h, enum mxq_linear_sched) ---------------------------------
+// plan_linear decides the schedule of every Linear entry point below and the workspace that schedule uses; run_plan launches
+// it.  The measured thresholds, each with the profile behind it (the whole map against hipBLASLt:
+// profiles/r04_dispatch_map.txt):
+
 // Token count from which hoisting the dequant out of the token loop (dequant pass + dense 256 x 256 kernel) beats the
 // fused kernel on the Llama shapes (tools/ab_gemm.py; profiles/r03_dense256.txt)
 static const int HOIST_MIN_TOKENS = 4096;
-// ... and the token count up to which the skinny kernel (one workgroup per 16-row block, every wave reads all of x from
-// L2) still beats it: its time grows with tokens x weight size, the split-K kernel's is flat up to 64 tokens.  Measured
-// crossovers (profiles/r03_midM.txt): ~44 tokens at 4096^2, ~22 at 11008 x 4096 and 4096 x 11008.
+// With a workspace, the token count up to which the skinny kernel (one workgroup per 16-row block, every wave reads all of x
+// from L2) still beats the split-K kernels: its time grows with tokens x weight size, the split-K kernel's is flat up to 64
+// tokens.  Measured crossovers (profiles/r03_midM.txt): ~44 tokens at 4096^2, ~22 at 11008 x 4096 and 4096 x 11008.
 static int skinny_max_tokens(int N, int K) { return (int64_t)N * K > ((int64_t)24 << 20) ? 20 : 40; }
-// ... and where the fused kernel's 128-token build (gemm8h.hip: 128 x 128 tiles) beats both neighbours, beyond 64 tokens:
+// The uniform layouts keep the skinny kernel up to 48 tokens, with or without a workspace, where the prefill kernel takes over;
+// without a workspace (the K range never split) the mixed layouts keep it up to 64 (19.5 us at 4096^2 where the 128 x 128-tile
+// kernel took 57).
+static const int SKINNY_MAX_UNIFORM = 48, SKINNY_NOWS_MIXED = 64;
+// Token counts the mid-M split-K kernel (midm.hip) may serve: above the skinny kernel's range, below the point where the
+// prefill kernel's 256 x 128 tiles win again (profiles/r03_midM.txt).  Since round 4 the fused kernel's 128- / 64-token builds
+// take most of that range when a full workspace is given: what is left to this kernel is 21 / 41 .. 64 tokens on launches of
+// <= 64 tiles (and up to 256 tokens where the workspace is too small for those builds, or absent).
+static const int MIDM_MAX_TOKENS = 256;
+// Beyond 64 tokens, where the fused kernel's 128-token build (gemm8h.hip: 128 x 128 tiles) beats both neighbours:
 //   * launches of <= 64 such tiles (a tile would be shared by >= 4 CUs): SLICES mode -- K cut into one slice per idle CU,
 //     fp32 slabs through the workspace, a combine launch: the mid-M kernel's schedule with the fused kernel's wave roles.
 //     128 tokens x 4096^2 19.3 us (mid-M kernel 21.1, hipBLASLt fp16 19.5), 256 tokens 22.4 (26.6), 4096 x 11008 at
@@ -316,87 +324,130 @@ static int skinny_max_tokens(int N, int K) { return (int64_t)N * K > ((int64_t)2
 //   * launches of 65 .. 176 tiles: ONE launch, stream-K over the otherwise idle CUs (at most 4 CUs per tile): gate/up
 //     (11008 x 4096) at 128 / 192 / 256 tokens 25.2 / 33.4 / 34.8 us against 30.7 / 46.2 / 47.2 (mid-M kernel); 4096^2 at
 //     384 / 512 tokens 26.2 / 28.8 against 34.9 / 35.7 (256-token tile).
-// Same-process A/B on the Llama shapes: profiles/r04_gemm8h.txt.  Returns 0 (neither), 1 (stream-K), 2 (slices).
-static int gemm8h_mode(int M, int N, size_t ws_bytes) {
-    if (M <= 64 || ws_bytes < mxq_gemm8h_workspace_bytes()) return 0;
-    const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
-    return tiles <= 64 ? 2 : tiles <= 176 ? 1 : 0;
-}
-// Up to 64 tokens the same again with a 64-token tile (gemm8q.hip), where it wins: 65 .. 176 tiles of 64 x 128 in stream-K
-// mode -- gate/up at 21-64 tokens: 20.6-20.9 us against 23.6-23.9 (skinny / mid-M kernel); with few tiles the mid-M kernel's
-// 64-token form is as fast (4096^2 at 64 tokens 13.6 against 14.5) and stays.  `no_midm`: the uniform layouts, which that
-// kernel does not serve, take the slices mode there (4096^2 at 49-64 tokens: 14.5 us against 30 on the 256-token tile).
-static int gemm8q_mode(int M, int N, size_t ws_bytes, bool no_midm) {
-    if (M > 64 || ws_bytes < mxq_gemm8q_workspace_bytes()) return 0;
-    const int tiles = (N + 127) / 128;
-    return tiles <= 64 ? (no_midm ? 2 : 0) : tiles <= 176 ? 1 : 0;
-}
-static int small_tile_launch(int M, int mode, const void* x, const void* qweight, const void* rowmeta, void* y, int N, int K,
-                             int layout, void* workspace, size_t ws_bytes, hipStream_t stream) {
-    // <= 64 tiles of 128 x 128 and a short K (<= 96 K-steps): the fp32 partial tiles are the cost, and the 128 x 64 tile
-    // (gemm8n.hip) halves them for the same number of workgroups -- 4096^2 at 65-128 tokens 16.0-16.2 us against 18.4-18.6
-    // (its slices mode: <= 64 tiles of 128 x 64), at 192 / 256 tokens 20.5 / 21.0 against 22.2 / 22.3 (stream-K mode); with
-    // K = 11008 its longer K loop costs more than the bytes save (24-25 against 22-23 us): profiles/r04_gemm8h.txt
-    if (M > 64 && mode == 2 && K <= 6144) {
-        const int tiles64 = ((M + 127) / 128) * ((N + 63) / 64);
-        return tiles64 <= 64
-                   ? mxq_launch_gemm8n_slices_f16(x, qweight, rowmeta, y, M, N, K, layout, workspace, ws_bytes, 0, stream)
-                   : mxq_launch_gemm8n_layout_f16(x, qweight, rowmeta, y, M, N, K, layout, workspace, ws_bytes, stream);
-    }
-    if (M <= 64)
-        return mode == 2 ? mxq_launch_gemm8q_slices_f16(x, qweight, rowmeta, y, M, N, K, layout, workspace, ws_bytes, 0, stream)
-                         : mxq_launch_gemm8q_layout_f16(x, qweight, rowmeta, y, M, N, K, layout, workspace, ws_bytes, stream);
-    return mode == 2 ? mxq_launch_gemm8h_slices_f16(x, qweight, rowmeta, y, M, N, K, layout, workspace, ws_bytes, 0, stream)
-                     : mxq_launch_gemm8h_layout_f16(x, qweight, rowmeta, y, M, N, K, layout, workspace, ws_bytes, stream);
-}
+// Same-process A/B on the Llama shapes: profiles/r04_gemm8h.txt.  Up to 64 tokens the same edges on 64 x 128 tiles
+// (gemm8q.hip), where it wins: 65 .. 176 tiles in stream-K mode -- gate/up at 21-64 tokens: 20.6-20.9 us against 23.6-23.9
+// (skinny / mid-M kernel); with few tiles the mid-M kernel's 64-token form is as fast (4096^2 at 64 tokens 13.6 against 14.5)
+// and stays.  The uniform layouts, which that kernel does not serve, take the slices mode there (4096^2 at 49-64 tokens:
+// 14.5 us against 30 on the 256-token tile).
+static const int SLICES_MAX_TILES = 64, STREAMK_MAX_TILES = 176;
+// <= 64 tiles of 128 x 128 and a short K (<= 96 K-steps): the fp32 partial tiles are the cost, and the 128 x 64 tile
+// (gemm8n.hip) halves them for the same number of workgroups -- 4096^2 at 65-128 tokens 16.0-16.2 us against 18.4-18.6
+// (its slices mode: <= 64 tiles of 128 x 64), at 192 / 256 tokens 20.5 / 21.0 against 22.2 / 22.3 (stream-K mode); with
+// K = 11008 its longer K loop costs more than the bytes save (24-25 against 22-23 us): profiles/r04_gemm8h.txt
+static const int SHORT_K_MAX = 6144;
 
-// The workspace-free schedule of EVERY layout (mxq_linear_f16, and the _ws entries when `workspace` is NULL): the K range is
-// never split.  Streaming GEMV (<= 4 tokens), skinny MFMA kernel as far as it goes (mixed layouts 64 tokens: 19.5 us at
-// 4096^2 where the 128 x 128-tile kernel took 57; uniform layouts 48), then -- mixed layouts -- the mid-M kernel with one
-// slice per tile up to 256 tokens (44-54 us at 4096^2: use a _ws entry where it matters; a shape beyond its 32-bit offsets
-// falls through), and the prefill kernel on whole tiles beyond.
-static int linear_noworkspace(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K, int layout,
-                              hipStream_t stream) {
+struct LinearPlan {
+    int sched;        // enum mxq_linear_sched
+    size_t ws_need;   // bytes of workspace this schedule uses (0: none): with that much the plan and the launch are the same
+};
+
+// ws_bytes 0: no workspace; scratch_bytes 0: no scratch.  Host-only: no device work beyond the CU count that the
+// *_workspace_bytes() helpers cache.
+static LinearPlan plan_linear(int M, int N, int K, int layout, size_t ws_bytes, size_t scratch_bytes) {
     const bool mixed = mxq_layout_is_mixed(layout);
-    if (M <= 4) return mxq_launch_gemv_layout_f16(x, qweight, rowmeta, y, M, N, K, layout, stream);
-    if (M <= (mixed ? 64 : 48)) return mxq_launch_skinny_f16(x, qweight, rowmeta, y, M, N, K, layout, stream);
-    if (mixed && M <= MIDM_MAX_TOKENS) {
-        const int e = mxq_launch_midm_f16(x, qweight, rowmeta, y, M, N, K, layout, nullptr, 0, 0, 0, stream);
-        if (e != MXQ_E_SHAPE) return e;
+    if (M >= HOIST_MIN_TOKENS && scratch_bytes >= (size_t)N * K * 2) return {MXQ_SCHED_HOISTED, 0};
+    if (M <= 4) return {MXQ_SCHED_GEMV, 0};
+    const bool midm = mixed && M <= MIDM_MAX_TOKENS && mxq_midm_fits(N, K);
+    if (!ws_bytes) {
+        if (M <= (mixed ? SKINNY_NOWS_MIXED : SKINNY_MAX_UNIFORM)) return {MXQ_SCHED_SKINNY, 0};
+        if (midm) return {MXQ_SCHED_MIDM, 0};                           // one slice per tile
+        // whole tiles: the 128 x 128-tile kernel while one tile row holds every token (exact metadata only)
+        return {layout == MXQ_LAYOUT_MIXED && M <= 128 ? MXQ_SCHED_TILE128 : MXQ_SCHED_FUSED256, 0};
     }
-    if (layout == MXQ_LAYOUT_MIXED) return mxq_launch_gemm_f16(x, qweight, rowmeta, y, M, N, K, stream);
-    return mxq_launch_gemm8_layout_f16(x, qweight, rowmeta, y, M, N, K, layout, nullptr, 0, stream);
+    if (M <= (mixed ? skinny_max_tokens(N, K) : SKINNY_MAX_UNIFORM)) return {MXQ_SCHED_SKINNY, 0};
+    const int tiles_m = (M + 127) / 128, tiles_n = (N + 127) / 128, tiles = tiles_m * tiles_n;
+    if (M <= 64) {
+        const size_t need = mxq_gemm8q_workspace_bytes();
+        if (ws_bytes >= need && tiles_n <= STREAMK_MAX_TILES && (tiles_n > SLICES_MAX_TILES || !mixed))
+            return {tiles_n > SLICES_MAX_TILES ? MXQ_SCHED_FUSED64_STREAMK : MXQ_SCHED_FUSED64_SLICES, need};
+    } else if (const size_t need = mxq_gemm8h_workspace_bytes(); tiles <= STREAMK_MAX_TILES && ws_bytes >= need) {
+        if (tiles > SLICES_MAX_TILES) return {MXQ_SCHED_FUSED128_STREAMK, need};
+        if (K > SHORT_K_MAX) return {MXQ_SCHED_FUSED128_SLICES, need};
+        return {tiles_m * ((N + 63) / 64) <= SLICES_MAX_TILES ? MXQ_SCHED_FUSED128N64_SLICES : MXQ_SCHED_FUSED128N64_STREAMK,
+                need};
+    }
+    if (midm) {
+        // the mid-M kernel's K slices: 128 x 128 fp32 partial tiles beyond the 64-KiB head, at most one slice per CU (the
+        // bytes of the 64-token build's workspace).  It needs room for two slices per output tile: with less it would run
+        // unsplit (44-54 us at 4096^2 where the prefill kernel's stream-K tail takes 34).
+        const size_t two_slices = 65536 + (size_t)tiles * 2 * 128 * 128 * sizeof(float);
+        const size_t one_per_cu = mxq_gemm8q_workspace_bytes();
+        if (ws_bytes >= two_slices) return {MXQ_SCHED_MIDM, two_slices > one_per_cu ? two_slices : one_per_cu};
+    }
+    return {MXQ_SCHED_FUSED256, mxq_gemm8_workspace_bytes()};   // stream-K tail where it pays (csrc/gemm8.hip launch8)
 }
 
-int mxq_linear_f16(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
-                   void* stream) {
+static int run_plan(int sched, const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K, int layout,
+                    void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, hipStream_t st) {
+    switch (sched) {
+        case MXQ_SCHED_GEMV: return mxq_launch_gemv_layout_f16(x, qweight, rowmeta, y, M, N, K, layout, st);
+        case MXQ_SCHED_SKINNY: return mxq_launch_skinny_f16(x, qweight, rowmeta, y, M, N, K, layout, st);
+        case MXQ_SCHED_MIDM: return mxq_launch_midm_f16(x, qweight, rowmeta, y, M, N, K, layout, ws, ws_bytes, 0, 0, st);
+        case MXQ_SCHED_FUSED64_STREAMK:
+            return mxq_launch_gemm8q_layout_f16(x, qweight, rowmeta, y, M, N, K, layout, ws, ws_bytes, st);
+        case MXQ_SCHED_FUSED64_SLICES:
+            return mxq_launch_gemm8q_slices_f16(x, qweight, rowmeta, y, M, N, K, layout, ws, ws_bytes, 0, st);
+        case MXQ_SCHED_FUSED128_STREAMK:
+            return mxq_launch_gemm8h_layout_f16(x, qweight, rowmeta, y, M, N, K, layout, ws, ws_bytes, st);
+        case MXQ_SCHED_FUSED128_SLICES:
+            return mxq_launch_gemm8h_slices_f16(x, qweight, rowmeta, y, M, N, K, layout, ws, ws_bytes, 0, st);
+        case MXQ_SCHED_FUSED128N64_STREAMK:
+            return mxq_launch_gemm8n_layout_f16(x, qweight, rowmeta, y, M, N, K, layout, ws, ws_bytes, st);
+        case MXQ_SCHED_FUSED128N64_SLICES:
+            return mxq_launch_gemm8n_slices_f16(x, qweight, rowmeta, y, M, N, K, layout, ws, ws_bytes, 0, st);
+        case MXQ_SCHED_FUSED256: return mxq_launch_gemm8_layout_f16(x, qweight, rowmeta, y, M, N, K, layout, ws, ws_bytes, st);
+        case MXQ_SCHED_TILE128: return mxq_launch_gemm1_f16(x, qweight, rowmeta, y, M, N, K, st);
+        case MXQ_SCHED_HOISTED:
+            return mxq_linear_f16_hoisted(x, qweight, rowmeta, y, M, N, K, layout, scratch, scratch_bytes, st);
+    }
+    return MXQ_E_SHAPE;
+}
+
+// the body of every Linear entry point: validation, plan, launch (a workspace or scratch of 0 bytes counts as none)
+static int linear(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K, int layout,
+                  void* workspace, size_t ws_bytes, void* scratch, size_t scratch_bytes, void* stream) {
     if (int e = linear_check(x, qweight, rowmeta, y, M, N, K)) return e;
-    return linear_noworkspace(x, qweight, rowmeta, y, M, N, K, MXQ_LAYOUT_MIXED, (hipStream_t)stream);
+    if (!layout_ok(layout)) return MXQ_E_SHAPE;
+    if ((workspace && !aligned16(workspace)) || (scratch && !aligned16(scratch))) return MXQ_E_ALIGN;
+    if (!workspace) ws_bytes = 0;
+    if (!scratch) scratch_bytes = 0;
+    const LinearPlan p = plan_linear(M, N, K, layout, ws_bytes, scratch_bytes);
+    return run_plan(p.sched, x, qweight, rowmeta, y, M, N, K, layout, ws_bytes ? workspace : nullptr, ws_bytes, scratch,
+                    scratch_bytes, (hipStream_t)stream);
+}
+
+int mxq_linear_f16(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K, void* stream) {
+    return linear(x, qweight, rowmeta, y, M, N, K, MXQ_LAYOUT_MIXED, nullptr, 0, nullptr, 0, stream);
+}
+
+int mxq_linear_f16_ws(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+    return linear(x, qweight, rowmeta, y, M, N, K, MXQ_LAYOUT_MIXED, workspace, workspace_bytes, nullptr, 0, stream);
+}
+
+int mxq_linear_f16_layout_ws(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
+                             int layout, void* workspace, size_t workspace_bytes, void* stream) {
+    return linear(x, qweight, rowmeta, y, M, N, K, layout, workspace, workspace_bytes, nullptr, 0, stream);
+}
+
+int mxq_linear_f16_auto(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K, int layout,
+                        void* workspace, size_t workspace_bytes, void* w16_scratch, size_t scratch_bytes, void* stream) {
+    return linear(x, qweight, rowmeta, y, M, N, K, layout, workspace, workspace_bytes, w16_scratch, scratch_bytes, stream);
+}
+
+int mxq_linear_schedule(int M, int N, int K, int layout, size_t workspace_bytes, size_t scratch_bytes) {
+    if (!shape_ok(N, K) || M <= 0 || !layout_ok(layout)) return MXQ_E_SHAPE;
+    return plan_linear(M, N, K, layout, workspace_bytes, scratch_bytes).sched;
 }
 
 size_t mxq_gemm_workspace_bytes(void) { return mxq_gemm8_workspace_bytes(); }
 
-// Bytes of workspace the dispatch of mxq_linear_f16_auto can use for THIS call (0: the call never touches a workspace --
-// GEMV, skinny kernel, hoisted mode with a scratch): what a caller that owns one workspace per captured graph allocates
-// instead of the maximum (mxq_gemm_workspace_bytes()).  Mirrors the dispatch above.
 size_t mxq_linear_workspace_need(int M, int N, int K, int layout, int hoisting) {
     if (!shape_ok(N, K) || M <= 0 || !layout_ok(layout)) return 0;
-    if (M <= 4 || (hoisting && M >= HOIST_MIN_TOKENS)) return 0;
-    const bool mixed = mxq_layout_is_mixed(layout);
-    if (M <= (mixed ? skinny_max_tokens(N, K) : 48)) return 0;
-    const size_t full = mxq_gemm8_workspace_bytes();
-    if (M > 64 ? gemm8h_mode(M, N, full) : gemm8q_mode(M, N, full, layout == MXQ_LAYOUT_W2G16 || layout == MXQ_LAYOUT_W4ROW)) {
-        size_t need = M > 64 ? mxq_gemm8h_workspace_bytes() : mxq_gemm8q_workspace_bytes();
-        if (M > 64 && mxq_gemm8n_workspace_bytes() > need) need = mxq_gemm8n_workspace_bytes();
-        return need;
-    }
-    if (mixed && M <= MIDM_MAX_TOKENS) {   // the mid-M kernel's partial tiles: one slice per idle CU, at most
-        const size_t tiles = (size_t)((M + 127) / 128) * ((N + 127) / 128);
-        size_t slabs = tiles > 256 ? tiles : 256 + tiles;
-        return (size_t)65536 + slabs * 128 * 128 * sizeof(float);
-    }
-    return full;
+    return plan_linear(M, N, K, layout, mxq_gemm8_workspace_bytes(), hoisting ? (size_t)N * K * 2 : 0).ws_need;
 }
+
+int mxq_hoist_min_tokens(void) { return HOIST_MIN_TOKENS; }
 
 // hipStreamGetCaptureInfo through THIS library's HIP runtime (the process's own: a caller that dlopens "libamdhip64.so" by
 // name may load a second runtime next to the one its framework bundles): *active = 1 and *id = the capture sequence's
@@ -446,73 +497,9 @@ static int gemm_ws(const void* x, const void* qweight, const void* rowmeta, void
                    void* workspace, size_t ws_bytes, hipStream_t stream) {
     // with a workspace the wave-specialised kernel wins at every token count (its stream-K split keeps all
     // CUs busy when there are few tiles: 64 tokens x 4096^2 34 us vs 57 us for the 128-row-tile kernel);
-    // without one (mxq_gemm_f16_ws variant 0 only: mxq_linear_f16_ws forwards to mxq_linear_f16) the 128 x 128 kernel
+    // without one the 128 x 128 kernel
     if (!workspace) return mxq_launch_gemm_f16(x, qweight, rowmeta, y, M, N, K, stream);
     return mxq_launch_gemm8_f16(x, qweight, rowmeta, y, M, N, K, workspace, ws_bytes, 0, stream);
-}
-
-// the mid-M kernel needs the workspace beyond its 64-KiB head for at least two slices' partial tiles per output tile;
-// with less it would run unsplit (44-54 us at 4096^2 where the prefill kernel's stream-K tail takes 34)
-static bool midm_ws_ok(int M, int N, size_t ws_bytes) {
-    const size_t tiles = (size_t)((M + 127) / 128) * ((N + 127) / 128);
-    return ws_bytes >= (size_t)65536 + tiles * 2 * 128 * 128 * sizeof(float);
-}
-
-int mxq_linear_f16_ws(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
-                      void* workspace, size_t workspace_bytes, void* stream) {
-    if (!workspace) return mxq_linear_f16(x, qweight, rowmeta, y, M, N, K, stream);   // the workspace-free dispatch
-    if (int e = linear_check(x, qweight, rowmeta, y, M, N, K)) return e;
-    if (!aligned16(workspace)) return MXQ_E_ALIGN;
-    if (M <= 4) return mxq_launch_gemv_f16(x, qweight, rowmeta, y, M, N, K, (hipStream_t)stream);
-    if (M <= skinny_max_tokens(N, K))
-        return mxq_launch_skinny_f16(x, qweight, rowmeta, y, M, N, K, MXQ_LAYOUT_MIXED, (hipStream_t)stream);
-    if (const int mode = M > 64 ? gemm8h_mode(M, N, workspace_bytes) : gemm8q_mode(M, N, workspace_bytes, false))
-        return small_tile_launch(M, mode, x, qweight, rowmeta, y, N, K, MXQ_LAYOUT_MIXED, workspace, workspace_bytes,
-                                 (hipStream_t)stream);
-    if (M <= MIDM_MAX_TOKENS && midm_ws_ok(M, N, workspace_bytes)) {
-        const int e = mxq_launch_midm_f16(x, qweight, rowmeta, y, M, N, K, MXQ_LAYOUT_MIXED, workspace, workspace_bytes, 0, 0,
-                                          (hipStream_t)stream);
-        if (e != MXQ_E_SHAPE) return e;      // a shape beyond its 32-bit offsets: the prefill kernel takes it
-    }
-    return gemm_ws(x, qweight, rowmeta, y, M, N, K, workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-int mxq_linear_f16_layout_ws(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
-                             int layout, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int e = linear_check(x, qweight, rowmeta, y, M, N, K)) return e;
-    if (!layout_ok(layout)) return MXQ_E_SHAPE;
-    if (workspace && !aligned16(workspace)) return MXQ_E_ALIGN;
-    if (!workspace) return linear_noworkspace(x, qweight, rowmeta, y, M, N, K, layout, (hipStream_t)stream);
-    if (layout == MXQ_LAYOUT_MIXED)
-        return mxq_linear_f16_ws(x, qweight, rowmeta, y, M, N, K, workspace, workspace_bytes, stream);
-    if (M <= 4) return mxq_launch_gemv_layout_f16(x, qweight, rowmeta, y, M, N, K, layout, (hipStream_t)stream);
-    // every layout: the skinny MFMA kernel up to the token count where the split-K / prefill kernels overtake it
-    if (M <= (layout == MXQ_LAYOUT_MIXEDC ? skinny_max_tokens(N, K) : 48))
-        return mxq_launch_skinny_f16(x, qweight, rowmeta, y, M, N, K, layout, (hipStream_t)stream);
-    if (const int mode = M > 64 ? gemm8h_mode(M, N, workspace_bytes)
-                                : gemm8q_mode(M, N, workspace_bytes, layout != MXQ_LAYOUT_MIXEDC))
-        return small_tile_launch(M, mode, x, qweight, rowmeta, y, N, K, layout, workspace, workspace_bytes, (hipStream_t)stream);
-    if (layout == MXQ_LAYOUT_MIXEDC) {
-        if (M <= MIDM_MAX_TOKENS && midm_ws_ok(M, N, workspace_bytes)) {
-            const int e = mxq_launch_midm_f16(x, qweight, rowmeta, y, M, N, K, layout, workspace, workspace_bytes, 0, 0,
-                                              (hipStream_t)stream);
-            if (e != MXQ_E_SHAPE) return e;
-        }
-    }
-    return mxq_launch_gemm8_layout_f16(x, qweight, rowmeta, y, M, N, K, layout, workspace, workspace_bytes,
-                                       (hipStream_t)stream);
-}
-
-int mxq_hoist_min_tokens(void) { return HOIST_MIN_TOKENS; }
-
-int mxq_linear_f16_auto(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K, int layout,
-                        void* workspace, size_t workspace_bytes, void* w16_scratch, size_t scratch_bytes, void* stream) {
-    if (int e = linear_check(x, qweight, rowmeta, y, M, N, K)) return e;
-    if (!layout_ok(layout)) return MXQ_E_SHAPE;
-    if (w16_scratch && !aligned16(w16_scratch)) return MXQ_E_ALIGN;
-    if (M >= HOIST_MIN_TOKENS && w16_scratch && scratch_bytes >= (size_t)N * K * 2)
-        return mxq_linear_f16_hoisted(x, qweight, rowmeta, y, M, N, K, layout, w16_scratch, scratch_bytes, stream);
-    return mxq_linear_f16_layout_ws(x, qweight, rowmeta, y, M, N, K, layout, workspace, workspace_bytes, stream);
 }
 
 int mxq_gemm_f16_ws(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
@@ -612,7 +599,7 @@ int mxq_gemm_awq_f16(const void* x, const void* kernel, const void* scales, cons
     if (workspace && !aligned16(workspace)) return MXQ_E_ALIGN;
     if (workspace && workspace_bytes < 65536) return MXQ_E_SHAPE;
     // Up to 32 tokens: a streaming kernel (one workgroup per 128 channels x K slice, last arriver sums the slices).  Beyond -- and as
-    // its fallback -- the fused kernel's dispatch by tile count (gemm8h_mode / gemm8q_mode above) on this operand format's builds:
+    // its fallback -- the fused kernel's dispatch by tile count (plan_linear above) on this operand format's builds:
     // 64-token tiles, then 128-token tiles while there are at most 176 of them (<= 1024 tokens) -- <= 64 tiles: every tile's K range cut so that tiles x slices fill the
     // chip, partial tiles summed by a combine launch; 65 .. 176 tiles: one launch, stream-K over the otherwise idle CUs (both need
     // the workspace) -- beyond that 256-token tiles, persistent, stream-K tail.

@@ -509,6 +509,11 @@ extern "C" int mxq_prof_midm_f16(const void* x, const void* qweight, const void*
 }
 #endif
 
+// 32-bit buffer offsets: one tile's rows of x, the whole packed weight
+bool mxq_midm_fits(int N, int K) {
+    return (int64_t)128 * K * 2 < ((int64_t)1 << 31) && (int64_t)(N / 16) * (K / 64) * MXQ_BLK_BYTES < ((int64_t)1 << 31);
+}
+
 // 1 <= M; layout MXQ_LAYOUT_MIXED or MXQ_LAYOUT_MIXEDC.  workspace (nullable): the shared GEMM workspace
 // (mxq_gemm_workspace_bytes); without one the K range is not split.  bm: 0 = by M, else 64 | 128; splits: 0 = by
 // the CU count, else the number of K slices asked for (clamped to what K and the workspace allow).
@@ -516,9 +521,7 @@ int mxq_launch_midm_f16(const void* x, const void* qweight, const void* rowmeta,
                         void* workspace, size_t ws_bytes, int bm, int splits, hipStream_t stream) {
     if (layout != MXQ_LAYOUT_MIXED && layout != MXQ_LAYOUT_MIXEDC) return -1;
     if (bm != 0 && bm != 64 && bm != 128) return -1;
-    // 32-bit buffer offsets: one tile's rows of x, the whole packed weight
-    if ((int64_t)128 * K * 2 >= ((int64_t)1 << 31) || (int64_t)(N / 16) * (K / 64) * MXQ_BLK_BYTES >= ((int64_t)1 << 31))
-        return -1;
+    if (!mxq_midm_fits(N, K)) return -1;
     if (bm == 0) bm = M <= 64 ? 64 : 128;
     const bool c = layout == MXQ_LAYOUT_MIXEDC;
     if (bm == 64)

@@ -111,14 +111,15 @@ int mxq_launch_gemm8_layout_f16(const void* x, const void* qweight, const void* 
                                 int layout, void* workspace, size_t ws_bytes, hipStream_t stream);
 int mxq_launch_gemv_f16(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
                         hipStream_t stream);
-// skinny MFMA kernel, 1 <= M <= 64 (skinny.hip; the dispatch uses it for 5..40 tokens with a workspace -- 20 for weights
-// beyond 24 M elements -- and up to 64 without one: capi.hip skinny_max_tokens); layout MXQ_LAYOUT_MIXED or MXQ_LAYOUT_MIXEDC
+// skinny MFMA kernel, 1 <= M <= 64 (skinny.hip; the token counts the dispatch gives it: capi.hip plan_linear); layout
+// MXQ_LAYOUT_MIXED or MXQ_LAYOUT_MIXEDC
 int mxq_launch_skinny_f16(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
                           int layout, hipStream_t stream);
 // mid-size token counts (48 < M <= ~1024): split-K over workgroups + combine (midm.hip); layout MXQ_LAYOUT_MIXED / MIXEDC;
 // workspace nullable (no split then); bm 0 | 64 | 128, splits 0 = automatic
 int mxq_launch_midm_f16(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K, int layout,
                         void* workspace, size_t ws_bytes, int bm, int splits, hipStream_t stream);
+bool mxq_midm_fits(int N, int K);   // the mid-M kernel's 32-bit offsets hold this weight (else MXQ_E_SHAPE)
 int mxq_launch_gemv_layout_f16(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N,
                                int K, int layout, hipStream_t stream);
 int mxq_launch_quantize_uniform(const void* W, int dtype, void* qweight, void* rowmeta, int N, int K, int layout,

@@ -59,7 +59,6 @@ _WS_MAILBOX_OFF = 65504   # bytes: 64-bit address of the workspace's host mailbo
 # MXQ_CHECK_WORKSPACE=1 checks synchronously after EVERY call instead (debugging).
 _MAILBOX: Dict[tuple, tuple] = {}     # key -> (pinned int32[4] tensor, its numpy view)
 _CHECK_EVERY_CALL = __import__("os").environ.get("MXQ_CHECK_WORKSPACE", "") not in ("", "0")
-MIDM_MAX_TOKENS = 256     # capi.hip: the most tokens mxq_linear_f16_ws may hand to the mid-M split-K kernel (no counters)
 
 
 _CAPTURE_KEYS: list = []          # capture workspaces in order of creation
@@ -439,27 +438,31 @@ def linear_dense(x: torch.Tensor, w16: torch.Tensor, out: Optional[torch.Tensor]
 
 
 GEMM_PATHS = {"gemm": 0, "fused": 0, "gemm1": 1, "gemm8": 8, "gemm9": 9, "midm": 10, "gemm8h": 12, "gemm8h_split": 13, "gemm8h_slices": 14, "gemm8q_split": 16, "gemm8q_slices": 17, "gemm8n_split": 20, "gemm8n_slices": 21}   # include/mxq_hip.h: enum mxq_gemm_variant
+# the paths of `linear` per layout code (_layout_code): the named kernels are the exact mixed layout's alone
+_PATHS = ("auto", "gemm", "gemv", "skinny", "whole", "hoist", "fused")
+_LAYOUT_PATHS = {0: frozenset(_PATHS + tuple(GEMM_PATHS)), 1: frozenset(_PATHS), 2: frozenset(_PATHS),
+                 3: frozenset(_PATHS + ("gemm8",))}
 
 
-def linear(x: torch.Tensor, p: PackedMXQ, out: Optional[torch.Tensor] = None, path: str = "auto") -> torch.Tensor:
-    """y = x @ dequant(p).T for x [..., K] fp16 -> [..., N] fp16 (fp32 accumulation).
+def linear(x: torch.Tensor, p, out: Optional[torch.Tensor] = None, path: str = "auto") -> torch.Tensor:
+    """y = x @ W.T for x [..., K] fp16 -> [..., N] fp16 (fp32 accumulation), W the dequantised weight of a PackedMXQ (mixed
+    layout, exact or compact metadata) or a PackedUniform.
 
-    path: "auto" (the library's own dispatch, mxq_linear_f16_auto: GEMV kernel for <= 4 tokens, skinny MFMA kernel up to 40 --
-    20 for weights beyond 24 M elements --, then by tile count the fused kernel's 64- / 128-token builds or the mid-M split-K
-    kernel, the 256-token fused kernel beyond, the hoisted mode from 4096 tokens: profiles/r04_dispatch_map.txt), "gemm",
-    "gemv", "midm",
-    "skinny" (1..64 tokens), "hoist" (dequant hoisted out of the token loop; "auto" / "gemm" take it from
-    HOIST_MIN_TOKENS tokens on), "fused" (never hoist), "whole" (fused kernel, whole tiles only), or an explicit GEMM
-    kernel: "gemm1" (128x128 tile), "gemm8" (256x128 tile, wave-specialised, persistent, stream-K tail), "gemm9"
-    (gemm8 splitting its tail whenever that is structurally possible: tests), "gemm8h" / "gemm8h_split" / "gemm8h_slices"
-    (its 128-token build: tail split where it pays / always / K slices + combine launch), "gemm8q_split" / "gemm8q_slices"
-    (the 64-token build)."""
+    path: "auto" (the library's own dispatch, mxq_linear_f16_auto: the schedules it picks are include/mxq_hip.h's enum
+    mxq_linear_sched), "gemv" (<= 4 tokens), "skinny" (1..64 tokens), "hoist" (dequant hoisted out of the token loop),
+    "gemm" (the fused kernel, hoisted from HOIST_MIN_TOKENS tokens on), "fused" (never hoisted), "whole" (fused kernel, whole
+    tiles only: no stream-K split, so a tile's sums do not depend on the launch's token count).  On the mixed layout with
+    exact metadata "gemm" / "fused" take the workspace (stream-K tail), and every kernel has a name (GEMM_PATHS,
+    include/mxq_hip.h enum mxq_gemm_variant): "gemm1" (128x128 tile), "gemm8" (256x128 tile, wave-specialised, persistent,
+    stream-K tail), "gemm9" (gemm8 splitting its tail whenever that is structurally possible: tests), "midm", "gemm8h" /
+    "gemm8h_split" / "gemm8h_slices" (its 128-token build: tail split where it pays / always / K slices + combine launch),
+    "gemm8q_*" (the 64-token build), "gemm8n_*" (the 128 x 64-tile build).  Compact metadata also has "gemm8" (= "fused")."""
     _need_gpu(x, p.qweight)
     if x.dtype != torch.float16:
         raise ValueError(f"activations must be float16 (W2/4 x A16), got {x.dtype}")
     if x.shape[-1] != p.K:
         raise ValueError(f"in_features mismatch: x has {x.shape[-1]}, weight has {p.K}")
-    if x.device != p.device:
+    if x.device != p.qweight.device:
         raise ValueError("x and the packed weight live on different devices")
     flat = x.dim() == 2 and x.is_contiguous()          # (the usual call: no view objects made on the way in or out)
     x2 = x if flat else x.reshape(-1, p.K).contiguous()
@@ -470,21 +473,17 @@ def linear(x: torch.Tensor, p: PackedMXQ, out: Optional[torch.Tensor] = None, pa
         raise ValueError("out must be a contiguous float16 [tokens, out_features] tensor")
     if M == 0:
         return out.reshape(*x.shape[:-1], p.N)
-    if path == "hoist":
-        return linear_hoisted(x, p, out=out)
     lib = _lib.load()
-    args = (x2.data_ptr(), p.qweight.data_ptr(), p.rowmeta.data_ptr(), out.data_ptr(), M, p.N, p.K)
-    if path == "auto" and M > 4:
-        # ONE C call for the whole dispatch (include/mxq_hip.h: mxq_linear_f16_auto): skinny / mid-M split-K / fused
-        # prefill kernel with its stream-K tail / hoisted-dequant mode, chosen inside the library by token count
-        hoists = M >= HOIST_MIN_TOKENS
-        st = _stream(x2)
-        lay = _layout_code(p)
+    lay = _layout_code(p)
+    args = (x2.data_ptr(), p.qweight.data_ptr(), p.rowmeta.data_ptr(), out.data_ptr(), M, p.N, p.K, lay)
+    st = _stream(x2)
+    if path == "auto":
+        # ONE C call for the whole dispatch; beyond the GEMV's token counts a workspace where the dispatch can use one
+        # and -- under capture -- only as big as this launch needs, a scratch where it may hoist
         with _on_device(x.device):
-            # (a workspace only where the dispatch can use one, and -- under capture -- only as big as this launch needs)
-            ws = gemm_workspace(x2.device, stream=st, need=lib.mxq_linear_workspace_need(M, p.N, p.K, lay, 1))
-            scratch = hoist_scratch(x2.device, lib.mxq_hoist_scratch_bytes(p.N, p.K)) if hoists else None
-            _lib.check(lib.mxq_linear_f16_auto(*args, lay, ws.data_ptr() if ws is not None else None,
+            ws = None if M <= 4 else gemm_workspace(x2.device, stream=st, need=lib.mxq_linear_workspace_need(M, p.N, p.K, lay, 1))
+            scratch = hoist_scratch(x2.device, lib.mxq_hoist_scratch_bytes(p.N, p.K)) if M >= HOIST_MIN_TOKENS else None
+            _lib.check(lib.mxq_linear_f16_auto(*args, ws.data_ptr() if ws is not None else None,
                                                ws.numel() if ws is not None else 0,
                                                scratch.data_ptr() if scratch is not None else None,
                                                scratch.numel() if scratch is not None else 0, st),
@@ -492,44 +491,31 @@ def linear(x: torch.Tensor, p: PackedMXQ, out: Optional[torch.Tensor] = None, pa
             if _CHECK_EVERY_CALL and ws is not None:
                 workspace_status(x2.device)
         return out if flat else out.reshape(*x.shape[:-1], p.N)
-    if path == "gemm" and M >= HOIST_MIN_TOKENS:
+    if path not in _LAYOUT_PATHS[lay]:
+        raise ValueError(f"path {path!r} is not available for the {type(p).__name__} weight's layout")
+    if path == "hoist" or (path == "gemm" and M >= HOIST_MIN_TOKENS):
         return linear_hoisted(x, p, out=out)
-    if path == "skinny":
-        with _on_device(x.device):
-            _lib.check(lib.mxq_skinny_f16(*args, 3 if p.compact else 0, _stream(x2)), "mxq_skinny_f16")
-        return out.reshape(*x.shape[:-1], p.N)
-    if path == "whole":   # the fused prefill kernel on whole tiles only (no workspace: no stream-K split, so a tile's sums
-        #                   do not depend on the launch's token count: tests compare launches of different sizes bit for bit)
-        with _on_device(x.device):
-            _lib.check(lib.mxq_gemm_f16_layout(*args, _layout_code(p), _stream(x2)), "mxq_gemm_f16_layout[whole]")
-        return out.reshape(*x.shape[:-1], p.N)
-    if p.compact:      # compact metadata: the layout entry points (same kernels, other field offsets)
-        if path not in ("auto", "gemm", "gemv", "gemm8", "fused"):
-            raise ValueError(f"path {path!r} is not available for compact metadata")
-        with _on_device(x.device):
-            fn = lib.mxq_gemv_f16_layout if path == "gemv" or (path == "auto" and M <= 4) else lib.mxq_gemm_f16_layout
-            _lib.check(fn(*args, 3, _stream(x2)), f"mxq_linear_f16[{path}, compact]")
-        return out.reshape(*x.shape[:-1], p.N)
+    ws = None
     with _on_device(x.device):
         if path == "gemv":
-            rc = lib.mxq_gemv_f16(*args, _stream(x2))
-        elif path == "auto" and M <= 4:                          # GEMV: no workspace involved
-            rc = lib.mxq_linear_f16(*args, _stream(x2))
-        else:
-            midm = path == "midm"
-            ws = (gemm_workspace(x2.device, counters=not midm)
-                  if path in ("auto", "gemm", "fused", "gemm8", "gemm9", "midm", "gemm8h", "gemm8h_split", "gemm8h_slices", "gemm8q_split", "gemm8q_slices", "gemm8n_split", "gemm8n_slices") else None)
-            wsp, wsn = (ws.data_ptr(), ws.numel()) if ws is not None else (None, 0)
-            if path == "auto":
-                rc = lib.mxq_linear_f16_ws(*args, wsp, wsn, _stream(x2))
-            elif path in GEMM_PATHS:
-                rc = lib.mxq_gemm_f16_ws(*args, GEMM_PATHS[path], wsp, wsn, _stream(x2))
-            else:
-                raise ValueError(f"unknown path {path!r}")
-        _lib.check(rc, f"mxq_linear_f16[{path}]")
-        if _CHECK_EVERY_CALL and path not in ("gemv",) and M > 4:
+            rc = lib.mxq_gemv_f16_layout(*args, st)
+        elif path == "skinny":
+            rc = lib.mxq_skinny_f16(*args, st)
+        elif path == "whole" or lay != 0:        # the fused kernel on whole tiles, no workspace
+            rc = lib.mxq_gemm_f16_layout(*args, st)
+        else:                                    # a named kernel of the mixed layout with exact metadata
+            ws = gemm_workspace(x2.device, counters=path != "midm") if path != "gemm1" else None
+            rc = lib.mxq_gemm_f16_ws(*args[:7], GEMM_PATHS[path], ws.data_ptr() if ws is not None else None,
+                                     ws.numel() if ws is not None else 0, st)
+        _lib.check(rc, f"linear[{path}]")
+        if _CHECK_EVERY_CALL and ws is not None:
             workspace_status(x2.device)
     return out.reshape(*x.shape[:-1], p.N)
+
+
+def linear_layout(x: torch.Tensor, p, out: Optional[torch.Tensor] = None, path: str = "gemm") -> torch.Tensor:
+    """The former layout entry, kept as a name for bench.py: `linear` with its old default path "gemm"."""
+    return linear(x, p, out=out, path=path)
 
 
 def linear_fused(x: torch.Tensor, p: PackedMXQ, prologue: int = 0, norm_w: Optional[torch.Tensor] = None,
@@ -657,47 +643,3 @@ def expand_uniform(p: PackedUniform, codes: bool = True):
         _lib.check(lib.mxq_expand_layout(p.qweight.data_ptr(), p.rowmeta.data_ptr(), w16.data_ptr(), *ptrs, N, K,
                                          LAYOUTS[p.layout], _stream(w16)), "mxq_expand_layout")
     return w16, out
-
-
-def linear_layout(x: torch.Tensor, p, out: Optional[torch.Tensor] = None, path: str = "gemm") -> torch.Tensor:
-    """Quantised Linear on a PackedMXQ (mixed) or PackedUniform weight: path "gemm" = MFMA dequant-GEMM at any
-    token count, "gemv" = the streaming GEMV (<= 4 tokens), "skinny" = the skinny MFMA kernel (<= 64 tokens), "auto" = the
-    library's dispatch (mxq_linear_f16_auto: GEMV up to 4 tokens, skinny kernel up to 48, fused GEMM, hoisted mode from
-    HOIST_MIN_TOKENS)."""
-    layout = LAYOUTS[getattr(p, "layout", "mixed")]
-    if layout == 0:
-        return linear(x, p, out=out, path=path)        # the mixed layout's default (fastest) kernels
-    _need_gpu(x, p.qweight)
-    if x.dtype != torch.float16 or x.shape[-1] != p.K:
-        raise ValueError("activations must be fp16 [..., in_features]")
-    x2 = x.reshape(-1, p.K).contiguous()
-    M = x2.shape[0]
-    if out is None:
-        out = torch.empty((M, p.N), dtype=torch.float16, device=x.device)
-    if path == "whole":
-        path = "fused"                                 # (uniform layouts: "fused" already runs without a workspace)
-    if path not in ("gemm", "gemv", "auto", "hoist", "fused", "skinny"):
-        raise ValueError(f"unknown path {path!r}")
-    if M == 0:
-        return out.reshape(*x.shape[:-1], p.N)
-    if path == "hoist" or (path == "gemm" and M >= HOIST_MIN_TOKENS):
-        return linear_hoisted(x, p, out=out)
-    lib = _lib.load()
-    args = (x2.data_ptr(), p.qweight.data_ptr(), p.rowmeta.data_ptr(), out.data_ptr(), M, p.N, p.K, layout)
-    with _on_device(x.device):
-        if path == "auto" and M > 4:        # the library's own dispatch: skinny kernel / fused prefill GEMM / hoisted mode
-            hoists = M >= HOIST_MIN_TOKENS
-            ws = gemm_workspace(x2.device, need=lib.mxq_linear_workspace_need(M, p.N, p.K, layout, 1))
-            scratch = hoist_scratch(x2.device, lib.mxq_hoist_scratch_bytes(p.N, p.K)) if hoists else None
-            _lib.check(lib.mxq_linear_f16_auto(*args, ws.data_ptr() if ws is not None else None,
-                                               ws.numel() if ws is not None else 0,
-                                               scratch.data_ptr() if scratch is not None else None,
-                                               scratch.numel() if scratch is not None else 0, _stream(x2)),
-                       "mxq_linear_f16_auto")
-        elif path == "skinny":
-            _lib.check(lib.mxq_skinny_f16(*args, _stream(x2)), "mxq_skinny_f16")
-        else:
-            fn, what = ((lib.mxq_gemv_f16_layout, "mxq_gemv_f16_layout") if path in ("gemv", "auto")
-                        else (lib.mxq_gemm_f16_layout, "mxq_gemm_f16_layout"))
-            _lib.check(fn(*args, _stream(x2)), what)
-    return out.reshape(*x.shape[:-1], p.N)

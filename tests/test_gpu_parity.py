@@ -515,11 +515,12 @@ def test_stream_k_partition_fuzz(dev, sk):
                                    (256, 11392, 1024)])    # ... and 178: the 256-token tile again
 @pytest.mark.parametrize("layout", ["mixed", "mixedc", "w2g16", "w4row"])
 def test_half_height_tile_through_the_dispatch(dev, M, N, K, layout):
-    """capi.hip gemm8h_mode / gemm8q_mode: beyond 64 tokens, launches of up to 176 tiles of 128 x 128 run the fused kernel's
-    128-token build (gemm8h.hip) -- up to 64 tiles in slices mode (K slices + combine launch), 65..176 in one launch with
-    stream-K over the idle CUs; up to 64 tokens the 64-token build (gemm8q.hip) where it wins -- every weight layout, through the product dispatch: against the fp32 product on the bit-exact dequantised
-    weight, twice with identical bits, counters left zero; for the mixed layout the dispatch's result IS the explicit path's."""
-    from mxq_amd import packing
+    """The dispatch (include/mxq_hip.h, enum mxq_linear_sched): beyond 64 tokens, launches of up to 176 tiles of 128 x 128 run
+    the fused kernel's 128-token build (gemm8h.hip) -- up to 64 tiles in slices mode (K slices + combine launch), 65..176 in one
+    launch with stream-K over the idle CUs; up to 64 tokens the 64-token build (gemm8q.hip) where it wins -- every weight layout,
+    through the product dispatch: against the fp32 product on the bit-exact dequantised weight, twice with identical bits,
+    counters left zero; for the mixed layout the dispatch's result IS the explicit path of the schedule it reports."""
+    from mxq_amd import _lib, packing
     g = torch.Generator(device=dev).manual_seed(M + N + K)
     W = (torch.randn(N, K, generator=g, device=dev) * 0.02).half()
     if layout in ("mixed", "mixedc"):
@@ -531,26 +532,25 @@ def test_half_height_tile_through_the_dispatch(dev, M, N, K, layout):
     x = torch.randn(M, K, generator=g, device=dev).half()
     wd = packing.dequant(p) if layout in ("mixed", "mixedc") else packing.expand_uniform(p, codes=False)[0]
     ws = packing.gemm_workspace(torch.device(dev))
-    y = packing.linear_layout(x, p, path="auto")
+    y = packing.linear(x, p, path="auto")
     r = x.float() @ wd.float().t()
     assert ((y.float() - r).abs().max() / r.abs().max()).item() <= REL_TOL
-    assert torch.equal(packing.linear_layout(x, p, path="auto"), y)
+    assert torch.equal(packing.linear(x, p, path="auto"), y)
     assert int(ws[:65504].view(torch.int32).abs().sum().item()) == 0 and int(ws[65520:65536].view(torch.int32).abs().sum().item()) == 0
-    tiles = -(-M // 128) * -(-N // 128)
-    if layout == "mixed" and M <= 64:
-        if 65 <= -(-N // 128) <= 176 and M > 20:
-            yq = packing.linear(x, p, path="gemm8q_split")      # the same kernel with its tail ALWAYS split: the dispatch
-            if K >= 4096:                                        # splits where that pays (it does from ~32 K-steps per tile on)
-                assert torch.equal(yq, y)
-            assert ((y.float() - yq.float()).abs().max() / r.abs().max()).item() <= REL_TOL
-    elif layout == "mixed" and tiles <= 64 and K <= 6144:       # short K: the 128 x 64 tile (half the partial-tile bytes)
-        t64 = -(-M // 128) * -(-N // 64)
-        yn = packing.linear(x, p, path="gemm8n_slices" if t64 <= 64 else "gemm8n_split")
-        if t64 <= 64 or K >= 4096:                               # (stream-K: the dispatch splits only where that pays)
-            assert torch.equal(yn, y)
-        assert ((y.float() - yn.float()).abs().max() / r.abs().max()).item() <= REL_TOL
-    elif layout == "mixed" and tiles <= 176:
-        assert torch.equal(packing.linear(x, p, path="gemm8h_slices" if tiles <= 64 else "gemm8h"), y)
+    if layout != "mixed":
+        return
+    sched = _lib.SCHED_NAMES[_lib.load().mxq_linear_schedule(M, N, K, 0, ws.numel(), 0)]
+    # schedule -> (the explicit path that runs the same kernel, bit-identical?): the explicit stream-K paths split the tail
+    # ALWAYS, the dispatch only where that pays (it does from ~32 K-steps per tile on)
+    path, same_bits = {"skinny": ("skinny", True), "midm": ("midm", True), "fused256": ("gemm8", True),
+                       "fused64_streamk": ("gemm8q_split", K >= 4096),
+                       "fused128n64_slices": ("gemm8n_slices", True), "fused128n64_streamk": ("gemm8n_split", K >= 4096),
+                       "fused128_slices": ("gemm8h_slices", True), "fused128_streamk": ("gemm8h", True)}[sched]
+    ye = packing.linear(x, p, path=path)
+    if same_bits:
+        assert torch.equal(ye, y), (sched, path)
+    assert ((y.float() - ye.float()).abs().max() / r.abs().max()).item() <= REL_TOL
+    if sched in ("fused128_slices", "fused128_streamk"):
         ym = packing.linear(x, p, path="midm")           # the neighbour it replaced here: equal up to summation order
         assert ((y.float() - ym.float()).abs().max() / r.abs().max()).item() <= REL_TOL
 
@@ -600,7 +600,7 @@ def test_linear_auto_c_entry_is_correct_on_every_path_it_dispatches_to(dev):
 @pytest.mark.parametrize("M", [3, 40, 64, 128, 256, 300])
 def test_workspace_free_dispatch_every_layout(dev, M):
     """mxq_linear_f16_layout_ws with workspace == NULL (and mxq_linear_f16): ONE workspace-free schedule for every layout
-    (capi.hip linear_noworkspace; ADVICE r4: compact metadata at 128 tokens used to take another road than exact metadata)
+    (include/mxq_hip.h, enum mxq_linear_sched; ADVICE r4: compact metadata at 128 tokens used to take another road than exact metadata)
     -- correct against the fp32 product on the kernel-dequantised weight at token counts either side of every threshold."""
     from mxq_amd import _lib, packing
     lib = _lib.load()
@@ -1140,7 +1140,7 @@ def test_config5_full_size_m32768(dev, layout, N, K):
         p = packing.quantize_pack_uniform(W, layout)
         wd = packing.expand_uniform(p, codes=False)[0]
     x = torch.randn(M, K, generator=g).half().to(dev)
-    y = packing.linear_layout(x, p)
+    y = packing.linear(x, p, path="gemm")
     worst_max = worst_fro = 0.0
     for r0 in range(0, M, 4096):                       # fp32 reference in slabs (keeps the fp32 copies small)
         ref = x[r0:r0 + 4096].float() @ wd.float().t()
@@ -1155,10 +1155,10 @@ def test_config5_full_size_m32768(dev, layout, N, K):
     _check_gemm(y[rows].cpu().numpy(), O.linear_ref(x[rows].cpu().numpy(), w_or), f"{layout} M=32768 rows vs oracle")
     for r0 in (0, M - 2048):
         xs = x[r0:r0 + 2048].contiguous()
-        alone = packing.linear_layout(xs, p, path="whole")          # whole tiles: the same sums in the same order
+        alone = packing.linear(xs, p, path="whole")          # whole tiles: the same sums in the same order
         assert torch.equal(alone, y[r0:r0 + 2048]), (layout, r0)
         # the dispatch may split the tail of a 2048-token launch along K (gate/up does since round 4): other summation order
-        disp = packing.linear_layout(xs, p)
+        disp = packing.linear(xs, p, path="gemm")
         assert ((disp.float() - alone.float()).abs().max() / alone.float().abs().max()).item() <= REL_TOL, (layout, r0)
 
 
@@ -1178,9 +1178,9 @@ def test_hoisted_dequant_mode_is_bit_identical_to_the_fused_gemm(dev, layout, M,
     else:
         p = packing.quantize_pack_uniform(W, layout)
         wd = packing.expand_uniform(p, codes=False)[0]
-    fused = packing.linear_layout(x, p, path="fused" if layout.startswith("mixed") else "gemm") if M < packing.HOIST_MIN_TOKENS \
+    fused = packing.linear(x, p, path="fused" if layout.startswith("mixed") else "gemm") if M < packing.HOIST_MIN_TOKENS \
         else None
-    hoisted = packing.linear_layout(x, p, path="hoist")
+    hoisted = packing.linear(x, p, path="hoist")
     ref = x.float() @ wd.float().t()
     assert ((hoisted.float() - ref).abs().max() / ref.abs().max()).item() <= REL_TOL
     if fused is not None and M % 256 == 0 and (M // 256) * ((N + 127) // 128) % 256 == 0:
@@ -1188,7 +1188,7 @@ def test_hoisted_dequant_mode_is_bit_identical_to_the_fused_gemm(dev, layout, M,
     elif fused is not None:
         assert ((hoisted.float() - fused.float()).abs().max() / ref.abs().max()).item() <= REL_TOL
     if M >= packing.HOIST_MIN_TOKENS:
-        assert torch.equal(packing.linear_layout(x, p, path="auto"), hoisted)
+        assert torch.equal(packing.linear(x, p, path="auto"), hoisted)
 
 
 @pytest.mark.parametrize("M,N,K", [(512, 512, 128), (300, 272, 256), (1000, 784, 4096), (8192, 4096, 256),
@@ -2125,12 +2125,12 @@ def test_uniform_gemv_vs_oracle(dev, layout, M, N, K):
     ref = O.uniform_quantize(W16.numpy(), layout)
     p = packing.quantize_pack_uniform(W16.to(dev), layout)
     x = torch.randn(M, K, generator=g).half()
-    y = packing.linear_layout(x.to(dev), p, path="gemv").cpu().numpy()
+    y = packing.linear(x.to(dev), p, path="gemv").cpu().numpy()
     _check_gemm(y, O.linear_ref(x.numpy(), ref["w_deq32"].astype(np.float16)), f"gemv {layout} {M}x{N}x{K}")
-    ya = packing.linear_layout(x.to(dev), p, path="auto").cpu().numpy()
+    ya = packing.linear(x.to(dev), p, path="auto").cpu().numpy()
     assert np.array_equal(ya, y)
     with pytest.raises(ValueError):
-        packing.linear_layout(torch.zeros(5, K, dtype=torch.float16, device=dev), p, path="gemv")
+        packing.linear(torch.zeros(5, K, dtype=torch.float16, device=dev), p, path="gemv")
 
 
 @pytest.mark.parametrize("layout", ["w2g16", "w4row"])
@@ -2145,12 +2145,12 @@ def test_uniform_skinny_vs_oracle(dev, layout, M, N, K):
     ref = O.uniform_quantize(W16.numpy(), layout)
     p = packing.quantize_pack_uniform(W16.to(dev), layout)
     x = torch.randn(M, K, generator=g).half()
-    y = packing.linear_layout(x.to(dev), p, path="skinny")
+    y = packing.linear(x.to(dev), p, path="skinny")
     _check_gemm(y.cpu().numpy(), O.linear_ref(x.numpy(), ref["w_deq32"].astype(np.float16)), f"skinny {layout} {M}x{N}x{K}")
     if M <= 48:
-        assert torch.equal(packing.linear_layout(x.to(dev), p, path="auto"), y), "auto dispatch should be the skinny kernel here"
+        assert torch.equal(packing.linear(x.to(dev), p, path="auto"), y), "auto dispatch should be the skinny kernel here"
     else:
-        _check_gemm(packing.linear_layout(x.to(dev), p, path="auto").cpu().numpy(),
+        _check_gemm(packing.linear(x.to(dev), p, path="auto").cpu().numpy(),
                     O.linear_ref(x.numpy(), ref["w_deq32"].astype(np.float16)), f"auto {layout} {M}x{N}x{K}")
 
 
@@ -2172,7 +2172,7 @@ def test_uniform_skinny_integer_exact(dev):
         assert np.array_equal(w16.cpu().numpy(), W), layout
         x = rng.integers(-2, 3, (M, K)).astype(np.float16)
         yref = x.astype(np.float32) @ W.astype(np.float32).T
-        y = packing.linear_layout(torch.from_numpy(x).to(dev), p, path="skinny").cpu().numpy().astype(np.float32)
+        y = packing.linear(torch.from_numpy(x).to(dev), p, path="skinny").cpu().numpy().astype(np.float32)
         assert np.array_equal(y, yref), layout
 
 
@@ -2189,7 +2189,7 @@ def test_uniform_gemm_vs_oracle(dev, layout, M, N, K):
     assert np.array_equal(got["codes"].cpu().numpy(), ref["codes"])
     w_ref16 = ref["w_deq32"].astype(np.float16)
     assert np.array_equal(w16.cpu().numpy().view(np.uint16), w_ref16.view(np.uint16))
-    y = packing.linear_layout(x.to(dev), p).cpu().numpy()
+    y = packing.linear(x.to(dev), p, path="gemm").cpu().numpy()
     _check_gemm(y, O.linear_ref(x.numpy(), w_ref16), f"{layout} {M}x{N}x{K}")
     if K >= 1024:   # rowmeta (16 B/row) is amortised over the row
         assert abs(p.bits_per_weight() - (4.5 if layout == "w2g16" else 4.0)) < 0.2

@@ -29,5 +29,5 @@ for _ in range(iters):
     elif layout == "mixed":
         packing.linear(x, p, out=out, path=variant)
     else:
-        packing.linear_layout(x, p, out=out)
+        packing.linear(x, p, out=out, path="gemm")
 torch.cuda.synchronize()

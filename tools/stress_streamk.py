@@ -65,7 +65,7 @@ def main():
             wd = packing.expand_uniform(p, codes=False)[0]
             path = "auto"
         x = torch.randn(M, K, generator=g, device=dev).half()
-        run = (lambda: packing.linear(x, p, path=path)) if layout == "mixed" else (lambda: packing.linear_layout(x, p, path="auto"))
+        run = lambda: packing.linear(x, p, path=path)
         y = run()
         err = 0.0
         for n0 in range(0, N, 4096):

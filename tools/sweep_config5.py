@@ -66,7 +66,7 @@ def main():
                 cases[(name, arm)] = dict(fn=(lambda x=x, W=W, out=out: torch.matmul(x, W.t(), out=out)), bpw=16.0, err=None)
                 continue
             p = packing.quantize_pack(W) if arm == "mixed" else packing.quantize_pack_uniform(W, arm)
-            fn = (lambda x=x, p=p, out=out: packing.linear_layout(x, p, out=out))
+            fn = (lambda x=x, p=p, out=out: packing.linear(x, p, out=out, path="gemm"))
             fn()
             # parity at the full size: fp32 product on the kernel-dequantised weight (bit-exact against the oracle in
             # tests/), 4096 sampled token rows; both error norms of SURVEY.md 8c
@@ -126,7 +126,7 @@ def main():
         out = torch.empty(M, N, device=dev, dtype=torch.float16)
         for arm in ("mixed", "w2g16", "w4row"):
             p = packing.quantize_pack(W) if arm == "mixed" else packing.quantize_pack_uniform(W, arm)
-            t = min(burst(lambda: packing.linear_layout(x, p, out=out, path="fused"), args.iters) for _ in range(3))
+            t = min(burst(lambda: packing.linear(x, p, out=out, path="fused"), args.iters) for _ in range(3))
             fused.setdefault(arm, []).append((name, N, K, mult, t))
         del W, x, out
     report["fused_at_full_size"] = {}
@@ -178,7 +178,7 @@ def main():
             for Mh in (1, 16):
                 xh = torch.randn(Mh, K, generator=g, device=dev).half()
                 oh = torch.empty(Mh, N, device=dev, dtype=torch.float16)
-                calls = [(lambda p=p: packing.linear_layout(xh, p, out=oh, path="auto")) for p in ws]
+                calls = [(lambda p=p: packing.linear(xh, p, out=oh, path="auto")) for p in ws]
                 us = graph_us(calls)
                 row[f"M{Mh}"] = {"us": round(us, 2), "GBps": round(nbytes / us / 1e3, 1), "pct_of_8TBps": round(nbytes / us / 1e3 / 80.0, 1)}
             hbm.append(row)
