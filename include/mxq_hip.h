@@ -40,6 +40,11 @@ extern "C" {
 #define MXQ_DTYPE_F16 1
 #define MXQ_DTYPE_BF16 2
 
+/* The head of a GEMM workspace (mxq_gemm_workspace_bytes, mxq_workspace_status below): counters, zero when idle. */
+#define MXQ_WS_HEAD_BYTES 65536        /* bytes of the head; partial tiles live beyond it */
+#define MXQ_WS_MAILBOX_OFFSET 65504    /* byte offset of the 8-byte address of the host mailbox (0: none) */
+#define MXQ_WS_STATUS_OFFSET 65520     /* byte offset of the four status ints (the head's last 16 bytes) */
+
 #define MXQ_E_SHAPE (-1)   /* N % 16, K % 64, sizes <= 0, unsupported group size ... */
 #define MXQ_E_NULL (-2)    /* a required pointer is NULL */
 #define MXQ_E_DTYPE (-3)   /* unknown dtype code */
@@ -105,7 +110,7 @@ int mxq_gemv_f16(const void* x, const void* qweight, const void* rowmeta, void* 
  * whose tile count is not a multiple of the CU count (stream-K tail, csrc/gemm8.hip): e.g. 512 tokens
  * x 4096^2 is 64 tiles, a quarter of the 256 CUs, unless every CU takes a quarter of a tile's K range.
  * `workspace` is device memory of at least mxq_gemm_workspace_bytes() bytes, 16-byte aligned, whose
- * first 64 KiB the caller zeroes ONCE (hipMemset) before first use; the kernels leave it zeroed, so
+ * first MXQ_WS_HEAD_BYTES the caller zeroes ONCE (hipMemset) before first use; the kernels leave it zeroed, so
  * it can be reused by every later launch on the SAME stream (launches on different streams need
  * different workspaces).  workspace == NULL (or 0 bytes) selects the workspace-free schedule of mxq_linear_f16.  The
  * schedule by token count, tile count and workspace: enum mxq_linear_sched below.  The prefill kernel splits its tail only
@@ -134,11 +139,15 @@ size_t mxq_gemm_workspace_bytes(void);
  * together -- the grid is at most one workgroup per CU -- so a stream-K launch must not share the device with another
  * kernel that ALSO waits on its own unscheduled workgroups (two stream-K launches on two streams can starve each other;
  * ordinary kernels only delay it).  Every wait is bounded (~4 M polls, seconds).  A wait that gives up is never silent:
- * the tile (or token block) whose partial sums did not arrive is written as NaN, and the last four ints of the workspace's
- * 64-KiB head become {code, tail-tile index, workgroup, count seen} (code 1: an owner's wait, 2: the all-contributors
- * reduction's; 0: nothing happened).  After a non-zero code the counters are inconsistent: zero the head again before the
- * workspace is reused.  mxq_workspace_status copies the four ints to `status4` (HOST memory) after synchronising `stream`
- * -- the one entry point of this library that synchronises. */
+ * the tile (or token block) whose partial sums did not arrive is written as NaN, and the four ints at byte
+ * MXQ_WS_STATUS_OFFSET of the workspace become {code, tail-tile index, workgroup, count seen} (code 1: an owner's wait, 2:
+ * the all-contributors reduction's; 0: nothing happened).  After a non-zero code the counters are inconsistent: zero the
+ * head again before the workspace is reused.  mxq_workspace_status copies the four ints to `status4` (HOST memory) after
+ * synchronising `stream` -- the one entry point of this library that synchronises.
+ * Host mailbox: the caller may write, right after zeroing the head, the 64-bit address of 4 ints of PINNED HOST memory
+ * (zeroed) at byte MXQ_WS_MAILBOX_OFFSET; 0 there means none.  The first wait that gives up then also stores the four status
+ * ints there with system-scope stores, the code last, so the caller sees it by reading its own memory without
+ * synchronising.  The caller clears the mailbox when it zeroes the head again. */
 int mxq_workspace_status(const void* workspace, size_t workspace_bytes, int* status4, void* stream);
 /* Measurement helper: one launch of 8 single-wave workgroups (one per XCD) writing {s_memtime, s_memrealtime (100 MHz), XCC id, 0}
  * as 4 x uint64 each into `out32_u64` (32 x uint64, device memory).  Two stamps on one stream around a timed region give the
@@ -159,7 +168,7 @@ int mxq_clock_stamp(void* out32_u64, void* stream);
  *     Otherwise, mixed layouts up to 256 tokens, MIDM when the workspace holds two partial tiles per output tile; FUSED256
  *     (stream-K tail where it pays) beyond.
  *   MIDM is skipped where its 32-bit offsets do not hold the weight.  SLICES: every tile's K range cut into one slice per
- *   idle CU, fp32 partial tiles in the workspace beyond its 64-KiB head, a combine launch; STREAMK: one launch, stream-K
+ *   idle CU, fp32 partial tiles in the workspace beyond its head, a combine launch; STREAMK: one launch, stream-K
  *   over the otherwise idle CUs. */
 enum mxq_linear_sched {
     MXQ_SCHED_GEMV = 1,                  /* streaming GEMV (csrc/gemv.hip) */
@@ -189,7 +198,7 @@ int mxq_gemm_f16_ws(const void* x, const void* qweight, const void* rowmeta, voi
                     int variant, void* workspace, size_t workspace_bytes, void* stream);
 /* mxq_linear_f16_ws for a weight in any layout (MXQ_LAYOUT_*: mixed with exact or compact metadata, W2G16, W4ROW), same
  * dispatch (enum mxq_linear_sched).  The mid-M split-K kernel (csrc/midm.hip: K cut into slices over the workgroups, fp32
- * partial tiles in the workspace beyond its first 64 KiB, summed in slice order by a second launch -- the reference
+ * partial tiles in the workspace beyond its head (MXQ_WS_HEAD_BYTES), summed in slice order by a second launch -- the reference
  * launcher's split_k_iters regime, gemm_cuda_gen.cu:429-475) does not touch the workspace's counters. */
 int mxq_linear_f16_layout_ws(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
                              int layout, void* workspace, size_t workspace_bytes, void* stream);

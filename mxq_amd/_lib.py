@@ -15,6 +15,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmxq_hip.so")
 
 DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2
+# a GEMM workspace's head: include/mxq_hip.h MXQ_WS_HEAD_BYTES, MXQ_WS_MAILBOX_OFFSET, MXQ_WS_STATUS_OFFSET
+WS_HEAD_BYTES, WS_MAILBOX_OFFSET, WS_STATUS_OFFSET = 65536, 65504, 65520
 # mxq_linear_schedule's result: include/mxq_hip.h enum mxq_linear_sched
 SCHED_NAMES = {1: "gemv", 2: "skinny", 3: "midm", 4: "fused64_streamk", 5: "fused64_slices", 6: "fused128_streamk",
                7: "fused128_slices", 8: "fused128n64_streamk", 9: "fused128n64_slices", 10: "fused256", 11: "tile128",

@@ -367,10 +367,10 @@ static LinearPlan plan_linear(int M, int N, int K, int layout, size_t ws_bytes, 
                 need};
     }
     if (midm) {
-        // the mid-M kernel's K slices: 128 x 128 fp32 partial tiles beyond the 64-KiB head, at most one slice per CU (the
+        // the mid-M kernel's K slices: 128 x 128 fp32 partial tiles beyond the head, at most one slice per CU (the
         // bytes of the 64-token build's workspace).  It needs room for two slices per output tile: with less it would run
         // unsplit (44-54 us at 4096^2 where the prefill kernel's stream-K tail takes 34).
-        const size_t two_slices = 65536 + (size_t)tiles * 2 * 128 * 128 * sizeof(float);
+        const size_t two_slices = MXQ_WS_HEAD_BYTES + (size_t)tiles * 2 * 128 * 128 * sizeof(float);
         const size_t one_per_cu = mxq_gemm8q_workspace_bytes();
         if (ws_bytes >= two_slices) return {MXQ_SCHED_MIDM, two_slices > one_per_cu ? two_slices : one_per_cu};
     }
@@ -483,14 +483,14 @@ int mxq_clock_stamp(void* out32_u64, void* stream) {
     return (int)hipGetLastError();
 }
 
-// The stream-K kernels' status words (csrc/gemm8.hip, SK_STATUS_OFF: the last 16 bytes of the 64-KiB head).  The ONE entry
+// The stream-K kernels' status words (MXQ_WS_STATUS_OFFSET: the last 16 bytes of the head).  The ONE entry
 // that synchronises: it waits for `stream`, then copies the four ints to the host.
 int mxq_workspace_status(const void* workspace, size_t workspace_bytes, int* status4, void* stream) {
     if (!workspace || !status4) return MXQ_E_NULL;
-    if (workspace_bytes < 65536) return MXQ_E_SHAPE;
+    if (workspace_bytes < MXQ_WS_HEAD_BYTES) return MXQ_E_SHAPE;
     hipError_t e = hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) return (int)e;
-    return (int)hipMemcpy(status4, (const char*)workspace + 65536 - 16, 16, hipMemcpyDeviceToHost);
+    return (int)hipMemcpy(status4, (const char*)workspace + MXQ_WS_STATUS_OFFSET, 16, hipMemcpyDeviceToHost);
 }
 
 static int gemm_ws(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
@@ -597,7 +597,7 @@ int mxq_gemm_awq_f16(const void* x, const void* kernel, const void* scales, cons
     if (IC % 64 != 0 || IC % group_size != 0) return MXQ_E_SHAPE;
     if (!aligned16(x) || !aligned16(scales) || !aligned16(y) || ((uintptr_t)kernel & 3) || ((uintptr_t)zeros & 3)) return MXQ_E_ALIGN;
     if (workspace && !aligned16(workspace)) return MXQ_E_ALIGN;
-    if (workspace && workspace_bytes < 65536) return MXQ_E_SHAPE;
+    if (workspace && workspace_bytes < MXQ_WS_HEAD_BYTES) return MXQ_E_SHAPE;
     // Up to 32 tokens: a streaming kernel (one workgroup per 128 channels x K slice, last arriver sums the slices).  Beyond -- and as
     // its fallback -- the fused kernel's dispatch by tile count (plan_linear above) on this operand format's builds:
     // 64-token tiles, then 128-token tiles while there are at most 176 of them (<= 1024 tokens) -- <= 64 tiles: every tile's K range cut so that tiles x slices fill the

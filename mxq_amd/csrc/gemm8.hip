@@ -45,6 +45,7 @@
 
 #include <type_traits>
 
+#include "../../include/mxq_hip.h"
 #include "mxq_dequant.h"
 #include "mxq_format.h"
 #include "mxq_kernels.h"
@@ -179,9 +180,10 @@ struct AwqU {
 // the previous burst's weights)
 [[maybe_unused]] constexpr int ABL_HALF_XDMA = 512, ABL_THIRD_DEQ = 8192;
 // stream-K diagnostics (profiling builds, correct results): 16384 = wall-clock stamps of the fix-up phases (100 MHz
-// s_memrealtime, MFMA wave 0 of every workgroup -> 8 u64 per workgroup at byte 32768 of the workspace head);
+// s_memrealtime, MFMA wave 0 of every workgroup -> 8 u64 per workgroup at byte SK_STAMP_OFF of the workspace head);
 // 32768 = the all-contributors reduction from 3 contributors per tile on (product: SK_DIST_MIN)
 [[maybe_unused]] constexpr int EXP_SKSTAMPS = 16384, EXP_SK_DIST3 = 32768;
+constexpr int SK_STAMP_OFF = 32768;   // bytes: the stamps' area in the workspace head
 // 65536 = fault injection for the expiry test (tests/test_gpu_parity.py, profiling library only): unit 0 never counts its
 // parked pieces and every wait gives up after 4096 polls -- the launch must end with the workspace's status words set and
 // the starved tiles poisoned, not with silently wrong sums
@@ -341,7 +343,7 @@ __device__ __forceinline__ void sk_stamp(int* cnt, int wave, int lane, int i) {
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
         __builtin_amdgcn_sched_barrier(0);
-        if (wave == 0 && lane == 0 && cnt) ((u64t*)((char*)cnt + 32768))[(int64_t)blockIdx.x * 8 + i] = t;
+        if (wave == 0 && lane == 0 && cnt) ((u64t*)((char*)cnt + SK_STAMP_OFF))[(int64_t)blockIdx.x * 8 + i] = t;
     }
 }
 
@@ -473,19 +475,22 @@ __device__ __forceinline__ void mma_prologue_issue(const XDma& xd, char* smem, i
 #endif
 constexpr int SK_SPIN_BOUND = 1 << 22;      // polls (each one agent-scope load + s_sleep: several seconds in all)
 template <int ABL> constexpr int sk_spin_bound() { return (ABL & EXP_SK_WITHHOLD) ? 4096 : SK_SPIN_BOUND; }
-// A wait that gives up must not pass for a result.  Status words at the END of the workspace's 64-KiB head (ints
-// SK_STATUS_OFF .. +3; the K-step counts, the "done" counts and the profiling stamps all lie below byte 49152):
+// A wait that gives up must not pass for a result.  Status words at the END of the workspace's head (ints
+// SK_STATUS_OFF .. +3, include/mxq_hip.h MXQ_WS_STATUS_OFFSET; the K-step counts, the "done" counts and the profiling
+// stamps all lie below the mailbox: static_asserts below SK_DONE_OFF):
 //   [0] code (0 = fine; 1 = an owner's wait expired, 2 = a wait of the all-contributors reduction expired)
 //   [1] tail-tile index, [2] workgroup, [3] the count it saw.
 // The first failure's details stay (later ones only keep [0] non-zero); the tile (or token block) whose operands never
 // arrived is written as NaN.  The counters are then inconsistent: the host re-zeroes the head before the workspace is used
 // again (mxq_workspace_status reports, packing.workspace_status raises and resets).
 // HOST MAILBOX (round 6): ints SK_MAILBOX_OFF, +1 of the head hold a 64-bit address of 4 ints of PINNED HOST memory (0: none;
-// written by the caller that owns the workspace, include/mxq_hip.h).  The first failure also stores its four status ints
-// there with system-scope stores -- the code last -- so the host sees an expired wait by reading its own memory, without
-// synchronising with the device: the product's next call on that workspace raises (mxq_amd/packing.py).  Costs nothing
-// unless a wait expires.
-constexpr int SK_STATUS_OFF = 16380, SK_MAILBOX_OFF = 16376;
+// written by the caller that owns the workspace, include/mxq_hip.h MXQ_WS_MAILBOX_OFFSET).  The first failure also stores
+// its four status ints there with system-scope stores -- the code last -- so the host sees an expired wait by reading its
+// own memory, without synchronising with the device: the product's next call on that workspace raises
+// (mxq_amd/packing.py).  Costs nothing unless a wait expires.
+constexpr int SK_STATUS_OFF = MXQ_WS_STATUS_OFFSET / sizeof(int), SK_MAILBOX_OFF = MXQ_WS_MAILBOX_OFFSET / sizeof(int);
+static_assert(MXQ_WS_MAILBOX_OFFSET % 8 == 0 && MXQ_WS_MAILBOX_OFFSET + 8 <= MXQ_WS_STATUS_OFFSET &&
+              MXQ_WS_STATUS_OFFSET + 4 * sizeof(int) <= MXQ_WS_HEAD_BYTES, "mailbox and status words lie inside the head");
 __device__ __forceinline__ void sk_fail(int* cnt, int code, int j, int seen, int lane) {
     if (lane == 0) {
         int* st = cnt + SK_STATUS_OFF;
@@ -510,6 +515,10 @@ __device__ __forceinline__ void sk_fail(int* cnt, int code, int j, int seen, int
 #endif
 constexpr int SK_DIST_MIN = MXQ_SK_DIST_MIN;       // from this many contributors on, ALL of them reduce the tile (sk_reduce_distributed)
 constexpr int SK_DONE_OFF = 4096;    // ints: per-tile "done" counts behind the per-(tile, wave) K-step counts
+// launch8 keeps units * 8 * N_MMA <= SK_DONE_OFF, so the done counts end below 2 * SK_DONE_OFF ints; the stamps of at most
+// 256 workgroups (one per CU) follow
+static_assert(2 * SK_DONE_OFF * sizeof(int) <= SK_STAMP_OFF, "done counts end below the stamps");
+static_assert(SK_STAMP_OFF + 256 * 8 * sizeof(u64t) <= MXQ_WS_MAILBOX_OFFSET, "stamps end below the mailbox");
 // (unit u holds step k iff bound(u) <= k < bound(u + 1), i.e. u = ceil((k + 1) units / S) - 1; every unit of an XCD with a tail
 //  holds at least one step -- launcher: S >= 4 units -- so the contributors are the contiguous range uf .. uf + C - 1.  Two
 //  integer divisions; a scan over the units costs 64 of them, ~5 us of vector-ALU time, and ran once per piece and per task
@@ -1663,8 +1672,6 @@ int cu_count() {
     return cus;
 }
 
-constexpr size_t CNT_BYTES = 64 * 1024;   // K-step counters at the head of the workspace (>= 8*units*N_MMA ints)
-
 template <int ABL, int LAYOUT = MXQ_LAYOUT_MIXED>
 static int launch8(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
                    void* workspace, size_t ws_bytes, bool force, hipStream_t stream G8_AWQ_PARAM) {
@@ -1683,8 +1690,8 @@ static int launch8(const void* x, const void* qweight, const void* rowmeta, void
     // occupancy calculator for THIS kernel's registers and LDS, once per device; if it does not (or the query fails) the
     // launch keeps whole tiles, which never wait
     const bool coresident = mxq_resident_workgroups<&G8_KERNEL<ABL, LAYOUT>>(THREADS, SMEM_BYTES) >= cus;
-    if (workspace && coresident && tiles % cus != 0 && units * 8 * N_MMA <= SK_DONE_OFF && (SK_DONE_OFF + units * 8) * sizeof(int) <= CNT_BYTES &&
-        ws_bytes >= CNT_BYTES + (size_t)cus * 2 * BM * BN * sizeof(float)) {
+    if (workspace && coresident && tiles % cus != 0 && units * 8 * N_MMA <= SK_DONE_OFF &&
+        ws_bytes >= MXQ_WS_HEAD_BYTES + (size_t)cus * 2 * BM * BN * sizeof(float)) {
         const int t8 = (tiles % cus) / 8;   // tail tiles per XCD (the first tail % 8 XCDs hold one more)
         // Splitting the tail saves the idle share of one tile time, (1 - tail/CUs) * NT K-steps of ~1 us, and costs the
         // pieces' extra prologues, the parked partials and -- most of it -- K-steps that run ~1.3 x slower than whole
@@ -1716,7 +1723,7 @@ static int launch8(const void* x, const void* qweight, const void* rowmeta, void
     const int grid = tail && 8 * units > dp_grid ? 8 * units : dp_grid;
     G8_KERNEL<ABL, LAYOUT><<<grid, THREADS, SMEM_BYTES, stream>>>(
         (const uint16_t*)x, (const uint32_t*)qweight, (const float4*)rowmeta, (uint16_t*)y, M, N, K, tiles_m, tiles_n,
-        dp_tiles, dp_grid, tail, units, (float*)((char*)workspace + CNT_BYTES), (int*)workspace G8_AWQ_ARG);
+        dp_tiles, dp_grid, tail, units, (float*)((char*)workspace + MXQ_WS_HEAD_BYTES), (int*)workspace G8_AWQ_ARG);
     return (int)hipGetLastError();
 }
 
@@ -1728,7 +1735,7 @@ static int launch8_slices(const void* x, const void* qweight, const void* rowmet
     const int NT = K / BK, tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN, tiles = tiles_m * tiles_n;
     if (S <= 0) S = cu_count() / tiles;               // (2-3 x as many slices, i.e. 2-3 workgroups per CU: no faster, profiles/r05_smalltile_slices.txt)
     if (S > NT / 4) S = NT / 4;                       // at least 4 K-steps per slice
-    const size_t room = workspace && ws_bytes > CNT_BYTES ? (ws_bytes - CNT_BYTES) / ((size_t)tiles * BM * BN * sizeof(float)) : 0;
+    const size_t room = workspace && ws_bytes > MXQ_WS_HEAD_BYTES ? (ws_bytes - MXQ_WS_HEAD_BYTES) / ((size_t)tiles * BM * BN * sizeof(float)) : 0;
     if ((size_t)S > room) S = (int)room;
     if (S <= 1) return launch8<0, LAYOUT>(x, qweight, rowmeta, y, M, N, K, nullptr, 0, false, stream G8_AWQ_ARG);
     if (M <= 0 || N <= 0 || K < BK || K % BK != 0 || N % (LAYOUT == LAYOUT_AWQ ? 8 : 16) != 0) return -1;
@@ -1736,7 +1743,7 @@ static int launch8_slices(const void* x, const void* qweight, const void* rowmet
         return -1;
     hipError_t e = mxq_set_dyn_lds_once<&G8_KERNEL<0, LAYOUT>>(SMEM_BYTES);
     if (e != hipSuccess) return (int)e;
-    float* slab = (float*)((char*)workspace + CNT_BYTES);
+    float* slab = (float*)((char*)workspace + MXQ_WS_HEAD_BYTES);
     G8_KERNEL<0, LAYOUT><<<tiles * S, THREADS, SMEM_BYTES, stream>>>(
         (const uint16_t*)x, (const uint32_t*)qweight, (const float4*)rowmeta, (uint16_t*)y, M, N, K, tiles_m, tiles_n, 0, 0,
         -S, 0, slab, nullptr G8_AWQ_ARG);
@@ -1751,7 +1758,7 @@ static int launch8_slices(const void* x, const void* qweight, const void* rowmet
 // [IC / G, OC / 8] -> y fp16 [M, OC].  slices = 0: whole tiles + stream-K tail (workspace: counter head + partial slots, nullable);
 // slices > 0 (or -1: one workgroup per CU): every tile's K range cut that many ways + combine launch; -2: stream-K with the
 // tail always split (launches of few tiles).
-size_t G8_SYM(, _workspace_bytes)() { return CNT_BYTES + (size_t)(cu_count() / 8 * 8) * 2 * BM * BN * sizeof(float); }
+size_t G8_SYM(, _workspace_bytes)() { return MXQ_WS_HEAD_BYTES + (size_t)(cu_count() / 8 * 8) * 2 * BM * BN * sizeof(float); }
 int G8_SYM(launch_, _f16)(const void* x, const void* kernel, const void* scales, const void* zeros, void* y, int M, int IC, int OC,
                          int G, void* workspace, size_t ws_bytes, int slices, hipStream_t stream) {
     if (M <= 0 || IC < BK || IC % BK != 0 || OC <= 0 || OC % 8 != 0 || G < 8 || G % 8 != 0 || IC % G != 0 || G >= 4096 || IC >= (1 << 20))
@@ -1780,7 +1787,7 @@ int G8_SYM(launch_, _slices_f16)(const void* x, const void* qweight, const void*
     return -1;
 }
 
-size_t G8_SYM(, _workspace_bytes)() { return CNT_BYTES + (size_t)(cu_count() / 8 * 8) * 2 * BM * BN * sizeof(float); }
+size_t G8_SYM(, _workspace_bytes)() { return MXQ_WS_HEAD_BYTES + (size_t)(cu_count() / 8 * 8) * 2 * BM * BN * sizeof(float); }
 
 int G8_SYM(launch_, _f16)(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
                          void* workspace, size_t ws_bytes, int force, hipStream_t stream) {

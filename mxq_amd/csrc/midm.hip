@@ -35,6 +35,7 @@
 // Rows beyond M / N and chunks beyond a slice's end read as zeros through the buffer descriptors' range checks.
 #include <hip/hip_runtime.h>
 
+#include "../../include/mxq_hip.h"
 #include "mxq_dequant.h"
 #include "mxq_format.h"
 #include "mxq_kernels.h"
@@ -458,8 +459,6 @@ int cu_count_() {
     return cus;
 }
 
-constexpr size_t WS_HEAD = 64 * 1024;   // the stream-K counters of gemm8 live at the head of the shared workspace: untouched here
-
 template <int BM, bool COMPACT>
 int launch_t(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K, void* workspace,
              size_t ws_bytes, int splits, hipStream_t stream) {
@@ -468,10 +467,10 @@ int launch_t(const void* x, const void* qweight, const void* rowmeta, void* y, i
     const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN, tiles = tiles_m * tiles_n;
     // slices: as many as keep tiles x S within one workgroup per CU, at least 2 double-steps (4 chunks) each
     int S = 1;
-    if (workspace && ws_bytes > WS_HEAD) {
+    if (workspace && ws_bytes > MXQ_WS_HEAD_BYTES) {
         S = splits > 0 ? splits : cu_count_() / tiles;
         if (S > NC / 4) S = NC / 4;
-        const size_t room = (ws_bytes - WS_HEAD) / ((size_t)tiles * G::SLAB * sizeof(float));
+        const size_t room = (ws_bytes - MXQ_WS_HEAD_BYTES) / ((size_t)tiles * G::SLAB * sizeof(float));
         if ((size_t)S > room) S = (int)room;
         if (S < 1) S = 1;
     }
@@ -480,7 +479,7 @@ int launch_t(const void* x, const void* qweight, const void* rowmeta, void* y, i
     S = (NC + cps - 1) / cps;                         // no empty slice
     hipError_t e = mxq_set_dyn_lds_once<&mxq_midm_f16_kernel<BM, COMPACT>>(G::SMEM);
     if (e != hipSuccess) return (int)e;
-    float* part = S > 1 ? (float*)((char*)workspace + WS_HEAD) : nullptr;
+    float* part = S > 1 ? (float*)((char*)workspace + MXQ_WS_HEAD_BYTES) : nullptr;
     mxq_midm_f16_kernel<BM, COMPACT><<<tiles * S, THREADS, G::SMEM, stream>>>(
         (const uint16_t*)x, (const uint32_t*)qweight, (const float4*)rowmeta, (uint16_t*)y, part, M, N, K, tiles_m,
         tiles_n, S, cps);

@@ -22,6 +22,7 @@
 //     then re-zeroes the counter.  Deterministic: the order of every sum is fixed.
 #include <hip/hip_runtime.h>
 
+#include "../../include/mxq_hip.h"
 #include "mxq_kernels.h"
 
 namespace {
@@ -34,7 +35,9 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef __amdgpu_buffer_rsrc_t rsrc_t;
 
 constexpr int BN = 128, NB = BN / 16;
-constexpr int CNT_BYTES = 64 * 1024;     // the workspace's counter head (shared with the stream-K kernels: zero when idle)
+// one counter per channel block at the workspace's head (shared with the stream-K kernels: zero when idle), at most this many bytes
+constexpr int CNT_MAX_BYTES = 16384;
+static_assert(CNT_MAX_BYTES <= MXQ_WS_MAILBOX_OFFSET, "counters end below the mailbox");
 
 __device__ __forceinline__ rsrc_t make_rsrc(const void* base, uint32_t bytes) {
     return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, 0x00020000);
@@ -272,13 +275,13 @@ int launch_nj(const void* x, const void* kernel, const void* scales, const void*
         if (S2 > S && (words2 > red2 ? words2 : red2) <= 78 * 1024) S = S2;
     }
     const size_t slot = (size_t)BN * 16 * NJ * sizeof(float);
-    if (!workspace || nblk * (int)sizeof(int) > 16384) S = 1;
-    while (S > 1 && ws_bytes < (size_t)CNT_BYTES + (size_t)nblk * S * slot) --S;
+    if (!workspace || nblk * (int)sizeof(int) > CNT_MAX_BYTES) S = 1;
+    while (S > 1 && ws_bytes < (size_t)MXQ_WS_HEAD_BYTES + (size_t)nblk * S * slot) --S;
     int steps = (NT + S - 1) / S;
     while (steps * 64 > 2304) {                              // the slice must fit the LDS: more slices if there is a workspace for them
-        if (!workspace || nblk * (int)sizeof(int) > 16384) return MXQ_NOT_MY_SHAPE;
+        if (!workspace || nblk * (int)sizeof(int) > CNT_MAX_BYTES) return MXQ_NOT_MY_SHAPE;
         ++S;
-        if (ws_bytes < (size_t)CNT_BYTES + (size_t)nblk * S * slot) return MXQ_NOT_MY_SHAPE;
+        if (ws_bytes < (size_t)MXQ_WS_HEAD_BYTES + (size_t)nblk * S * slot) return MXQ_NOT_MY_SHAPE;
         steps = (NT + S - 1) / S;
     }
     S = (NT + steps - 1) / steps;                            // no empty slice
@@ -291,7 +294,7 @@ int launch_nj(const void* x, const void* kernel, const void* scales, const void*
     const uint32_t gmul = (uint32_t)(((uint64_t)1 << 32) / (uint32_t)G) + 1u;
     mxq_skinny_awq_f16_kernel<NJ, WAVES><<<nblk * S, THREADS, smem, stream>>>(
         (const uint16_t*)x, (const uint32_t*)kernel, (const uint16_t*)scales, (const uint32_t*)zeros, (uint16_t*)y, M, IC, OC, gmul, IC / G, S,
-        rows_per_slice, (int*)workspace, workspace ? (float*)((char*)workspace + CNT_BYTES) : nullptr);
+        rows_per_slice, (int*)workspace, workspace ? (float*)((char*)workspace + MXQ_WS_HEAD_BYTES) : nullptr);
     return (int)hipGetLastError();
 }
 

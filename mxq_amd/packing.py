@@ -13,6 +13,7 @@ Reference semantics implemented by the kernels:
 """
 from __future__ import annotations
 
+from collections import deque
 from dataclasses import dataclass
 from typing import Dict, Optional
 
@@ -47,24 +48,44 @@ def _on_device(device: torch.device):
     return _NOCTX if idx is None or idx == torch.cuda.current_device() else torch.cuda.device(device)
 
 
-_WORKSPACES: Dict[tuple, torch.Tensor] = {}
-_WS_EAGER: Dict[tuple, bool] = {}    # key -> the counter head has been zeroed (eagerly, or by a memset recorded in its graph)
-_WS_HEAD = 65536      # bytes of K-step counters at the head of a workspace (include/mxq_hip.h)
-_WS_MAILBOX_OFF = 65504   # bytes: 64-bit address of the workspace's host mailbox (csrc/gemm8.hip SK_MAILBOX_OFF)
-# A stream-K wait that expires (include/mxq_hip.h) writes the affected tile as NaN and flags the workspace.  The flag must reach
-# the CALLER without anybody polling: every workspace owns 4 ints of pinned host memory ("mailbox") whose address sits in its
-# head; the kernel stores its status there with system-scope stores, and every later hand-out of that workspace -- i.e. the next
-# packing.linear / QuantLinear.forward call on it -- reads the mailbox (plain host memory, no synchronisation) and raises.  A
-# starved launch therefore cannot feed NaN activations into a model for more than the launches already queued behind it.
-# MXQ_CHECK_WORKSPACE=1 checks synchronously after EVERY call instead (debugging).
-_MAILBOX: Dict[tuple, tuple] = {}     # key -> (pinned int32[4] tensor, its numpy view)
+class _Workspace:
+    """A cached GEMM workspace (``buf``) and what it owns.
+
+    ``capture_id``: the capture sequence that created it, None for an eager workspace.  ``head_ready``: its head has been
+    zeroed -- eagerly, or by a memset recorded into its graph.
+
+    A stream-K wait that expires (include/mxq_hip.h) writes the affected tile as NaN and flags the workspace.  The flag must
+    reach the CALLER without anybody polling: every eager workspace owns 4 ints of pinned host memory (``mailbox``, a numpy
+    view of ``box``) whose address sits in its head; the kernel stores its status there with system-scope stores, and every
+    later hand-out of that workspace -- i.e. the next packing.linear / QuantLinear.forward call on it -- reads the mailbox
+    (plain host memory, no synchronisation) and raises.  A starved launch therefore cannot feed NaN activations into a model
+    for more than the launches already queued behind it.  MXQ_CHECK_WORKSPACE=1 checks synchronously after EVERY call
+    instead (debugging).  (Capture workspaces have none: pinning host memory is not a capturable operation, and a captured
+    graph's launches are replayed without passing through here -- they are watched by workspace_status() alone.)"""
+    __slots__ = ("key", "dev", "buf", "capture_id", "box", "mailbox", "head_ready")
+
+    def __init__(self, key: tuple, buf: torch.Tensor, capture_id: Optional[int]):
+        self.key, self.dev, self.buf, self.capture_id = key, key[0], buf, capture_id
+        self.box = torch.zeros(4, dtype=torch.int32).pin_memory() if capture_id is None else None
+        self.mailbox = self.box.numpy() if self.box is not None else None
+        self.head_ready = False
+
+    def reset(self) -> None:
+        """Clear the mailbox, zero the head and write the mailbox's address into it (stream-ordered; under capture the device
+        operations are recorded into the graph)."""
+        self.buf[:_lib.WS_HEAD_BYTES].zero_()
+        if self.box is not None:
+            self.mailbox[:] = 0
+            self.buf[_lib.WS_MAILBOX_OFFSET:_lib.WS_MAILBOX_OFFSET + 8].view(torch.int64).fill_(self.box.data_ptr())
+        self.head_ready = True
+
+
+_WORKSPACES: Dict[tuple, _Workspace] = {}   # (device, stream) or (device, "capture", capture id, bytes) -> workspace
 _CHECK_EVERY_CALL = __import__("os").environ.get("MXQ_CHECK_WORKSPACE", "") not in ("", "0")
-
-
-_CAPTURE_KEYS: list = []          # capture workspaces in order of creation
 # A capture workspace lives in its graph's private memory pool; this cache holds a reference so that the memory cannot be
 # handed to a later capture that shares the pool while the first graph still replays on it (ADVICE r4).  The price is that
 # the bytes stay pinned after their graph is gone, so the cache is bounded -- generously: 256 graphs of <= 67 MB.
+_CAPTURES: deque = deque()      # capture workspaces in order of creation
 _MAX_CAPTURE_WS = 256
 
 
@@ -91,7 +112,7 @@ def gemm_workspace(device: torch.device, counters: bool = True, stream: Optional
     mxq_linear_workspace_need; None = the maximum) sizes them: a graph whose launches never leave the skinny kernel gets
     none at all (``need`` 0 returns None), one that stays within the small-tile builds a 34-MB buffer instead of 67 MB
     (two size classes per graph at most).  A buffer born under capture is never zeroed for real until a replay runs: its
-    first counters hand-out records ONE memset of the 64-KiB counter head into the graph.
+    first counters hand-out records ONE memset of the counter head into the graph.
 
     ``counters=False``: the caller's kernel uses the buffer beyond the head only (the mid-M kernel's partial tiles):
     no memset is recorded for it."""
@@ -108,64 +129,55 @@ def gemm_workspace(device: torch.device, counters: bool = True, stream: Optional
     if dev_index != torch.cuda.current_device() or torch.cuda.is_current_stream_capturing():
         capturing, cid = _capture_id(stream)
     if capturing:
-        nbytes = full if need is None or 2 * need > full else (full + _WS_HEAD) // 2     # two size classes
+        nbytes = full if need is None or 2 * need > full else (full + _lib.WS_HEAD_BYTES) // 2     # two size classes
         nbytes = max(nbytes, need or 0)
         key = (dev_index, "capture", cid, nbytes)
+        ws = _WORKSPACES.get(key)
+        if ws is None:                      # a bigger buffer of the same graph serves a smaller need
+            ws = _WORKSPACES.get((dev_index, "capture", cid, full))
     else:
         nbytes, key = full, (dev_index, stream)
-    ws = _WORKSPACES.get(key)
-    if ws is None and capturing:             # a bigger buffer of the same graph serves a smaller need
-        ws = _WORKSPACES.get((dev_index, "capture", cid, full))
-        if ws is not None:
-            key = (dev_index, "capture", cid, full)
+        ws = _WORKSPACES.get(key)
     if ws is None:
-        ws = _WORKSPACES[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        if not capturing:
-            # (eager workspaces only: pinning host memory is not a capturable operation, and a captured graph's launches
-            #  are replayed without passing through here -- its workspace is watched by workspace_status() alone)
-            box = torch.zeros(4, dtype=torch.int32).pin_memory()
-            _MAILBOX[key] = (box, box.numpy())
-        if capturing:
-            _WS_EAGER[key] = False                    # ... until a counters hand-out has recorded the memset
-            _CAPTURE_KEYS.append(key)
-            while len(_CAPTURE_KEYS) > _MAX_CAPTURE_WS:
-                old = _CAPTURE_KEYS.pop(0)
-                _WORKSPACES.pop(old, None)
-                _WS_EAGER.pop(old, None)
-                _MAILBOX.pop(old, None)
+        ws = _WORKSPACES[key] = _Workspace(key, torch.empty(nbytes, dtype=torch.uint8, device=device),
+                                           cid if capturing else None)
+        if capturing:                       # zeroed when a counters hand-out records the memset (below)
+            _CAPTURES.append(ws)
+            if len(_CAPTURES) > _MAX_CAPTURE_WS:
+                del _WORKSPACES[_CAPTURES.popleft().key]
         else:
-            _WS_EAGER[key] = True
-            _zero_head(ws, key)
-    else:
-        box = _MAILBOX.get(key)
-        if box is not None and box[1][0] != 0:        # a launch that ran on this workspace since the last hand-out gave up a wait
-            _raise_expired(key, ws)
-    if capturing and counters and not _WS_EAGER.get(key, False):
-        _zero_head(ws, key)                            # recorded once per graph and buffer (memset + the mailbox's address)
-        _WS_EAGER[key] = True
-    return ws
+            ws.reset()
+    elif ws.mailbox is not None and ws.mailbox[0] != 0:   # a launch that ran on this workspace since the last hand-out gave up a wait
+        _raise_expired(ws)
+    if capturing and counters and not ws.head_ready:
+        ws.reset()                          # recorded once per graph and buffer
+    return ws.buf
 
 
-def _zero_head(ws: torch.Tensor, key) -> None:
-    """Zero a workspace's 64-KiB head and write the address of its host mailbox into it (stream-ordered; under capture both
-    operations are recorded into the graph)."""
-    ws[:_WS_HEAD].zero_()
-    box = _MAILBOX.get(key)
-    if box is not None:
-        ws[_WS_MAILBOX_OFF:_WS_MAILBOX_OFF + 8].view(torch.int64).fill_(box[0].data_ptr())
+def _cached_by_device(device: Optional[torch.device]) -> Dict[int, list]:
+    """The cached workspaces by device index: all devices', or ``device``'s alone."""
+    only = None if device is None else (device.index if device.index is not None else torch.cuda.current_device())
+    by_dev: Dict[int, list] = {}
+    for ws in _WORKSPACES.values():
+        if only is None or ws.dev == only:
+            by_dev.setdefault(ws.dev, []).append(ws)
+    return by_dev
 
 
-def _raise_expired(key, ws: torch.Tensor):
-    """The mailbox of ``ws`` is set: report, clear it, make the workspace usable again (synchronises), raise."""
-    box, view = _MAILBOX[key]
-    st = [int(v) for v in view]
-    dev_index = key[0]
-    torch.cuda.synchronize(dev_index)
-    view[:] = 0
+def _reset_synchronised(dev_index: int, workspaces) -> None:
+    """Reset ``workspaces`` (all on device ``dev_index``) after the device's queued work, and wait for the resets."""
     with torch.cuda.device(dev_index):
-        _zero_head(ws, key)
         torch.cuda.synchronize(dev_index)
-    raise RuntimeError(f"stream-K wait expired on workspace {key}: [code, tail tile, workgroup, count seen] = {st}; the affected "
+        for ws in workspaces:
+            ws.reset()
+        torch.cuda.synchronize(dev_index)
+
+
+def _raise_expired(ws: _Workspace):
+    """The mailbox of ``ws`` is set: report, make the workspace usable again (synchronises), raise."""
+    st = [int(v) for v in ws.mailbox]
+    _reset_synchronised(ws.dev, [ws])
+    raise RuntimeError(f"stream-K wait expired on workspace {ws.key}: [code, tail tile, workgroup, count seen] = {st}; the affected "
                        "output tiles of that launch are NaN (results computed since then on this stream are suspect); the "
                        "workspace has been reset")
 
@@ -221,23 +233,19 @@ def workspace_status(device: Optional[torch.device] = None, reset: bool = True) 
     import ctypes
     lib = _lib.load()
     bad = []
-    for key, ws in list(_WORKSPACES.items()):
-        dev_index = key[0]
-        if device is not None and (device.index if device.index is not None else torch.cuda.current_device()) != dev_index:
-            continue
-        st = (ctypes.c_int * 4)()
+    st = (ctypes.c_int * 4)()
+    for dev_index, workspaces in _cached_by_device(device).items():
+        flagged = []
         with torch.cuda.device(dev_index):
             torch.cuda.synchronize(dev_index)          # (capture workspaces have no eager stream of their own)
-            _lib.check(lib.mxq_workspace_status(ws.data_ptr(), ws.numel(), ctypes.cast(st, ctypes.c_void_p), None),
-                       "mxq_workspace_status")
-            if st[0] != 0:
-                bad.append((key, list(st)))
-                if reset:
-                    box = _MAILBOX.get(key)
-                    if box is not None:
-                        box[1][:] = 0
-                    _zero_head(ws, key)
-                    torch.cuda.synchronize(dev_index)
+            for ws in workspaces:
+                _lib.check(lib.mxq_workspace_status(ws.buf.data_ptr(), ws.buf.numel(), ctypes.cast(st, ctypes.c_void_p), None),
+                           "mxq_workspace_status")
+                if st[0] != 0:
+                    bad.append((ws.key, list(st)))
+                    flagged.append(ws)
+        if reset and flagged:
+            _reset_synchronised(dev_index, flagged)
     if bad:
         raise RuntimeError("stream-K wait expired (workspace key, [code, tail tile, workgroup, count seen]): "
                            f"{bad}; the affected output tiles are NaN" + ("; counter heads re-zeroed" if reset else ""))
@@ -247,16 +255,8 @@ def reset_gemm_workspace(device: Optional[torch.device] = None):
     """Re-zero the counter heads of the cached stream-K workspaces (all devices, or one).  Needed only after a
     GEMM launch was aborted mid-kernel (device reset, killed process sharing the buffer): the kernels themselves
     always leave the counters zeroed.  Synchronises the device(s) involved."""
-    for key, ws in list(_WORKSPACES.items()):
-        dev_index = key[0]
-        if device is None or (device.index if device.index is not None else torch.cuda.current_device()) == dev_index:
-            torch.cuda.synchronize(dev_index)
-            box = _MAILBOX.get(key)
-            if box is not None:
-                box[1][:] = 0
-            with torch.cuda.device(dev_index):
-                _zero_head(ws, key)
-            torch.cuda.synchronize(dev_index)
+    for dev_index, workspaces in _cached_by_device(device).items():
+        _reset_synchronised(dev_index, workspaces)
 
 
 def _need_gpu(*ts: torch.Tensor):

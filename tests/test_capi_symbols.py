@@ -33,6 +33,15 @@ def test_every_declared_symbol_is_exported_and_bound(lib):
     assert sorted(_lib.SIGNATURES) == names
 
 
+def test_workspace_head_layout_mirrors_the_header():
+    """mxq_amd/_lib.py's copy of the workspace head's layout is the header's #defines."""
+    from mxq_amd import _lib
+    text = open(os.path.join(ROOT, "include", "mxq_hip.h")).read()
+    defs = {k: int(v) for k, v in re.findall(r"^#define (MXQ_WS_[A-Z_]+) (\d+)\b", text, flags=re.M)}
+    assert defs == {"MXQ_WS_HEAD_BYTES": _lib.WS_HEAD_BYTES, "MXQ_WS_MAILBOX_OFFSET": _lib.WS_MAILBOX_OFFSET,
+                    "MXQ_WS_STATUS_OFFSET": _lib.WS_STATUS_OFFSET}
+
+
 def test_version_and_size_helpers(lib):
     assert lib.mxq_version() >> 16 == 1
     assert lib.mxq_qweight_bytes(4096, 4096) == 256 * 64 * 576

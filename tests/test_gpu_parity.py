@@ -43,6 +43,13 @@ def _check_gemm(y, yref, what=""):
     return emax, efro
 
 
+def _assert_head_clean(ws, what=""):
+    """A workspace's head is zero everywhere but its mailbox address: the counters are left zeroed, no status is set."""
+    from mxq_amd import _lib
+    assert int(ws[:_lib.WS_MAILBOX_OFFSET].view(torch.int32).abs().sum().item()) == 0, what
+    assert int(ws[_lib.WS_STATUS_OFFSET:_lib.WS_HEAD_BYTES].view(torch.int32).abs().sum().item()) == 0, what
+
+
 # ----------------------------------------------------------------------------------------
 # quantise + pack + unpack + dequant
 # ----------------------------------------------------------------------------------------
@@ -427,7 +434,7 @@ def test_gemm_stream_k_tail(dev, M, N, K, sk):
     y = packing.linear(xd, p, path=sk)
     _check_gemm(y.cpu().numpy(), O.linear_ref(x.numpy(), w16), f"{sk} {M}x{N}x{K}")
     ws = packing.gemm_workspace(xd.device)
-    assert int(ws[:65504].view(torch.int32).abs().sum().item()) == 0 and int(ws[65520:65536].view(torch.int32).abs().sum().item()) == 0
+    _assert_head_clean(ws)
     for _ in range(3):
         assert torch.equal(packing.linear(xd, p, path=sk), y)
     y5 = packing.linear(xd, p, path="gemm1")
@@ -439,7 +446,7 @@ def test_gemm_stream_k_tail(dev, M, N, K, sk):
     if sk == "gemm8h_split":      # the 128-token build of the same kernel, splitting only where it pays
         yh = packing.linear(xd, p, path="gemm8h")
         assert ((y.float() - yh.float()).abs().max() / y5.float().abs().max()).item() <= 1e-3
-        assert int(ws[:65504].view(torch.int32).abs().sum().item()) == 0 and int(ws[65520:65536].view(torch.int32).abs().sum().item()) == 0
+        _assert_head_clean(ws)
 
 
 @pytest.mark.parametrize("M,N,K", [(640, 11008, 4096),     # 258 tiles: a 2-tile tail on 256 CUs (Llama gate/up at 640-768 tokens)
@@ -465,7 +472,7 @@ def test_gemm_small_tail_stream_k_through_the_dispatch(dev, M, N, K):
             worst = max(worst, ((y[:, n0:n0 + 8192].float() - r).abs().max() / r.abs().max()).item())
         assert worst <= REL_TOL, (path, worst)
         assert torch.equal(packing.linear(x, p, path=path), y), path
-        assert int(ws[:65504].view(torch.int32).abs().sum().item()) == 0 and int(ws[65520:65536].view(torch.int32).abs().sum().item()) == 0, path
+        _assert_head_clean(ws, path)
     # the split changes the summation order of the tail tiles only: whole-tile launch within rounding
     yw = packing.linear(x, p, path="whole")
     assert ((y.float() - yw.float()).abs().max() / yw.float().abs().max()).item() <= REL_TOL
@@ -492,7 +499,7 @@ def test_stream_k_partition_fuzz(dev, sk):
         assert err <= REL_TOL, (M, N, K, err)
         assert torch.equal(packing.linear(x, p, path=sk).float(), y), (M, N, K)
     ws = packing.gemm_workspace(torch.device(dev))
-    assert int(ws[:65504].view(torch.int32).abs().sum().item()) == 0 and int(ws[65520:65536].view(torch.int32).abs().sum().item()) == 0
+    _assert_head_clean(ws)
 
 
 @pytest.mark.parametrize("M,N,K", [(192, 11008, 4096),     # 2 x 86 = 172 tiles of 128 x 128: Llama gate/up, 129-256 tokens
@@ -536,7 +543,7 @@ def test_half_height_tile_through_the_dispatch(dev, M, N, K, layout):
     r = x.float() @ wd.float().t()
     assert ((y.float() - r).abs().max() / r.abs().max()).item() <= REL_TOL
     assert torch.equal(packing.linear(x, p, path="auto"), y)
-    assert int(ws[:65504].view(torch.int32).abs().sum().item()) == 0 and int(ws[65520:65536].view(torch.int32).abs().sum().item()) == 0
+    _assert_head_clean(ws)
     if layout != "mixed":
         return
     sched = _lib.SCHED_NAMES[_lib.load().mxq_linear_schedule(M, N, K, 0, ws.numel(), 0)]
@@ -668,8 +675,7 @@ def test_stream_k_wait_expiry_is_visible(dev, M, N, K, build, how):
             packing.workspace_status(xd.device)
         else:
             packing.linear(xd, p, path=path)                    # the product's own next call: no status query anywhere
-    assert int(ws[:65504].view(torch.int32).abs().sum().item()) == 0          # head re-zeroed (its last bytes: mailbox address, status)
-    assert int(ws[65520:65536].view(torch.int32).abs().sum().item()) == 0
+    _assert_head_clean(ws)                                      # head re-zeroed (its last bytes: mailbox address, status)
     again = packing.linear(xd, p, path=path)
     assert torch.equal(again, good)
     packing.workspace_status(xd.device)
@@ -728,10 +734,10 @@ def test_stream_k_launch_beside_an_lds_heavy_kernel(dev):
                                              "the test proves nothing")
 
 
-def test_stream_k_gemm_in_graphs_and_on_two_streams(dev):
+def test_stream_k_gemm_in_graphs_and_on_two_streams_with_own_workspaces(dev):
     """The stream-K GEMM leaves its workspace counters zeroed, so a captured launch can be replayed; and
     launches on different streams use different workspaces, so they may overlap."""
-    from mxq_amd import packing
+    from mxq_amd import _lib, packing
     p, w16, g = _packed_case(dev, 2048, 4096, 5)
     x = torch.randn(512, 4096, generator=g).half().to(dev)
     ref = packing.linear(x, p, path="gemm9")                      # warm-up: allocates this stream's workspace
@@ -752,14 +758,14 @@ def test_stream_k_gemm_in_graphs_and_on_two_streams(dev):
             outs.append([packing.linear(x, p, path="gemm9") for _ in range(8)])
     torch.cuda.synchronize()
     assert all(torch.equal(o, ref) for lst in outs for o in lst)
-    keys = {k for k in packing._WORKSPACES if k[0] == x.device.index}
-    assert len(keys) >= 3                                          # default stream + two side streams
+    mine = [w for w in packing._WORKSPACES.values() if w.dev == x.device.index]
+    assert len([w for w in mine if w.capture_id is None]) >= 3     # default stream + two side streams
     # every captured graph owns its workspace (keyed by the capture sequence's id): ONE memset of the counter head is
     # recorded per graph, and whatever the buffer holds before a replay does not matter
-    ckeys = [k for k in packing._WORKSPACES if k[0] == x.device.index and len(k) >= 3 and k[1] == "capture"]
-    assert len(ckeys) >= 1
-    for k in ckeys:
-        packing._WORKSPACES[k][:65536].fill_(7)
+    captured = [w for w in mine if w.capture_id is not None]
+    assert len(captured) >= 1
+    for w in captured:
+        w.buf[:_lib.WS_HEAD_BYTES].fill_(7)
     for _ in range(2):
         out.zero_()
         graph.replay()
@@ -770,7 +776,7 @@ def test_stream_k_gemm_in_graphs_and_on_two_streams(dev):
 @pytest.mark.parametrize("M,N,K", [(128, 4096, 4096),      # slices mode: two launches (K slices, combine) per call
                                    (192, 11008, 4096),     # the 128-token build, stream-K in one launch
                                    (48, 11008, 4096)])     # the 64-token build, stream-K
-def test_small_tile_dispatch_in_a_graph(dev, M, N, K):
+def test_small_tile_dispatch_in_a_graph_ignores_workspace_contents(dev, M, N, K):
     """The dispatch's small-tile paths under hipGraph capture: three calls per graph (the workspace's slabs / counters are
     reused from call to call inside the graph), replayed with the workspace overwritten in between -- equal to the eager
     result every time."""
@@ -784,18 +790,18 @@ def test_small_tile_dispatch_in_a_graph(dev, M, N, K):
     with torch.cuda.graph(graph):
         for x, o in zip(xs, outs):
             packing.linear(x, p, out=o, path="auto")
-    ckeys = [k for k in packing._WORKSPACES if len(k) >= 3 and k[1] == "capture"]
+    captured = [w for w in packing._WORKSPACES.values() if w.capture_id is not None]
     for it in range(3):
         for o in outs:
             o.zero_()
         if it:
-            packing._WORKSPACES[ckeys[-1]].fill_(it)      # whatever the buffer holds before a replay must not matter
+            captured[-1].buf.fill_(it)                    # whatever the buffer holds before a replay must not matter
         graph.replay()
         torch.cuda.synchronize()
         assert all(torch.equal(o, r) for o, r in zip(outs, refs)), it
 
 
-def test_two_stream_k_graphs_replayed_concurrently(dev):
+def test_two_stream_k_graphs_replayed_concurrently_on_own_workspaces(dev):
     """Two graphs with stream-K launches (partial tiles + counters in the workspace), replayed AT THE SAME TIME on two
     streams, many times: each graph has its own workspace, so neither corrupts the other's partial sums (round 3 shared
     one buffer per device among all captured launches)."""
@@ -813,8 +819,8 @@ def test_two_stream_k_graphs_replayed_concurrently(dev):
     with torch.cuda.graph(gb):
         for _ in range(4):
             packing.linear(xb, pb, out=outb, path="gemm9")
-    ckeys = [k for k in packing._WORKSPACES if len(k) >= 3 and k[1] == "capture"]
-    assert len({packing._WORKSPACES[k].data_ptr() for k in ckeys}) >= 2
+    captured = [w for w in packing._WORKSPACES.values() if w.capture_id is not None]
+    assert len({w.buf.data_ptr() for w in captured}) >= 2
     s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
     for _ in range(10):
         outa.zero_(); outb.zero_()
