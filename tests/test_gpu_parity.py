@@ -50,6 +50,14 @@ def _assert_head_clean(ws, what=""):
     assert int(ws[_lib.WS_STATUS_OFFSET:_lib.WS_HEAD_BYTES].view(torch.int32).abs().sum().item()) == 0, what
 
 
+def _poisoned_out(ws, like):
+    """Before a repeat: the workspace beyond its head refilled with 0xFF bytes (NaN as fp32 partials) and a NaN-filled
+    output, so a repeat cannot pass on the previous call's partial slots or output."""
+    from mxq_amd import _lib
+    ws[_lib.WS_HEAD_BYTES:].fill_(0xFF)
+    return torch.full_like(like, float("nan"))
+
+
 # ----------------------------------------------------------------------------------------
 # quantise + pack + unpack + dequant
 # ----------------------------------------------------------------------------------------
@@ -436,7 +444,7 @@ def test_gemm_stream_k_tail(dev, M, N, K, sk):
     ws = packing.gemm_workspace(xd.device)
     _assert_head_clean(ws)
     for _ in range(3):
-        assert torch.equal(packing.linear(xd, p, path=sk), y)
+        assert torch.equal(packing.linear(xd, p, out=_poisoned_out(ws, y), path=sk), y)
     y5 = packing.linear(xd, p, path="gemm1")
     assert ((y.float() - y5.float()).abs().max() / y5.float().abs().max()).item() <= 1e-3
     # the default dispatch is the same kernel, splitting only where it pays: equal up to summation order
@@ -471,7 +479,7 @@ def test_gemm_small_tail_stream_k_through_the_dispatch(dev, M, N, K):
             r = x.float() @ wd[n0:n0 + 8192].float().t()
             worst = max(worst, ((y[:, n0:n0 + 8192].float() - r).abs().max() / r.abs().max()).item())
         assert worst <= REL_TOL, (path, worst)
-        assert torch.equal(packing.linear(x, p, path=path), y), path
+        assert torch.equal(packing.linear(x, p, out=_poisoned_out(ws, y), path=path), y), path
         _assert_head_clean(ws, path)
     # the split changes the summation order of the tail tiles only: whole-tile launch within rounding
     yw = packing.linear(x, p, path="whole")
@@ -497,8 +505,8 @@ def test_stream_k_partition_fuzz(dev, sk):
         r = (x.float() @ packing.dequant(p).float().t())
         err = ((y - r).abs().max() / r.abs().max()).item()
         assert err <= REL_TOL, (M, N, K, err)
-        assert torch.equal(packing.linear(x, p, path=sk).float(), y), (M, N, K)
-    ws = packing.gemm_workspace(torch.device(dev))
+        ws = packing.gemm_workspace(torch.device(dev))
+        assert torch.equal(packing.linear(x, p, out=_poisoned_out(ws, y.half()), path=sk).float(), y), (M, N, K)
     _assert_head_clean(ws)
 
 
@@ -542,7 +550,7 @@ def test_half_height_tile_through_the_dispatch(dev, M, N, K, layout):
     y = packing.linear(x, p, path="auto")
     r = x.float() @ wd.float().t()
     assert ((y.float() - r).abs().max() / r.abs().max()).item() <= REL_TOL
-    assert torch.equal(packing.linear(x, p, path="auto"), y)
+    assert torch.equal(packing.linear(x, p, out=_poisoned_out(ws, y), path="auto"), y)
     _assert_head_clean(ws)
     if layout != "mixed":
         return
@@ -780,7 +788,7 @@ def test_small_tile_dispatch_in_a_graph_ignores_workspace_contents(dev, M, N, K)
     """The dispatch's small-tile paths under hipGraph capture: three calls per graph (the workspace's slabs / counters are
     reused from call to call inside the graph), replayed with the workspace overwritten in between -- equal to the eager
     result every time."""
-    from mxq_amd import packing
+    from mxq_amd import _lib, packing
     g = torch.Generator(device=dev).manual_seed(M + N)
     p = packing.quantize_pack((torch.randn(N, K, generator=g, device=dev) * 0.02).half())
     xs = [torch.randn(M, K, generator=g, device=dev).half() for _ in range(3)]
@@ -794,8 +802,10 @@ def test_small_tile_dispatch_in_a_graph_ignores_workspace_contents(dev, M, N, K)
     for it in range(3):
         for o in outs:
             o.zero_()
-        if it:
-            captured[-1].buf.fill_(it)                    # whatever the buffer holds before a replay must not matter
+        if it:                                            # whatever the buffer holds before a replay must not matter:
+            buf = captured[-1].buf                        # beyond the head NaN (0xFF) / 3.4e38 (0x7F) as fp32 partials
+            buf[:_lib.WS_HEAD_BYTES].fill_(it)
+            buf[_lib.WS_HEAD_BYTES:].fill_((0xFF, 0x7F)[it - 1])
         graph.replay()
         torch.cuda.synchronize()
         assert all(torch.equal(o, r) for o, r in zip(outs, refs)), it
