@@ -18,16 +18,18 @@ contained (mxq_amd/pipeline.py: Watchdog, init_group, run_guarded): 120-s proces
 phase and a hard one below the driver's limit -- a stuck rank prints its stacks and exits 86, a failed rank exits
 non-zero at once with a rank-tagged traceback -- and rank 0's line carries every rank's own account of the timed
 region (`per_rank`: its GEMMs' device time, the time its stream waited for the hop in / for a send slot, bytes
-hopped, stream-K status, shader clock) and, in `decode_pipeline.per_rank`, each stage's time per token and the
-round trip of the hidden row to the next rank.
+hopped, stream-K status, shader clock) and, with --full, in `decode_pipeline.per_rank`, each stage's time per token
+and the round trip of the hidden row to the next rank.
 
 Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (mxq_gemm8_f16_kernel,
 MFMA-bound): algorithmic 2*M*N*K flops of the launches of one step / their device time measured
-with HIP events on the launch stream; `roofline.traffic` = HBM-side bytes per launch from rocprofv3
-PMC child passes made in this run (live_traffic).  The other BASELINE configs ride along as side
-figures with their own roofline fractions: `decode_1gpu` (configs[2]), `fakequant_block` (configs[3]),
-`config5` (configs[4]); `--figure NAME` runs one of them alone.  `cpu_baseline` times the CPU restatement of the
-reference's dequant + F.linear (oracle/cpu_linear.py) on a bounded sample, rank 0 / N = 1 only.
+with HIP events on the launch stream; `roofline.traffic` = HBM-side bytes per launch, the committed constant from
+rocprofv3 PMC passes (profiles/r0N_gemm8_traffic.json).  A plain run does no more than the headline needs: set-up, warm-up,
+the timed steps, --dump-outputs and the line.  `--full` adds what takes runs of its own: `roofline.traffic` from rocprofv3
+PMC child passes made in this run (live_traffic); the other BASELINE configs as side figures with their own roofline
+fractions: `fused_launches_figure`, `decode_1gpu` (configs[2]), `fakequant_block` (configs[3]), `config5` (configs[4]);
+`cpu_baseline`, which times the CPU restatement of the reference's dequant + F.linear (oracle/cpu_linear.py) on a bounded
+sample (N = 1); and for N > 1 the `decode_pipeline` figure.  `--figure NAME` runs one side figure alone.
 `--dump-outputs DIR` (N = 1) writes a fixed sample of every Linear's output of the last timed step as DIR/<linear>.npy
 (dump_outputs); weights and inputs are seeded, so two builds given the same arguments can be compared output for output.
 """
@@ -459,10 +461,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else too: roofline.traffic from rocprofv3 PMC child passes, "
+                         "the fused-launch figure, the other BASELINE configs and the CPU baseline (N = 1), the decode "
+                         "pipeline figure (N > 1).  Without it the process launches nothing but the headline's kernels")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--headline-only", action="store_true",
-                    help="no side figures and no CPU baseline: the process launches nothing but the headline's kernels "
-                         "(what tools/prof_round.sh traces, so that the trace's per-kernel average is the headline's)")
     ap.add_argument("--figure", choices=["decode_1gpu", "fakequant_block", "config5"], default=None,
                     help="run ONE side figure only and print it (no headline): what tools/prof_round.sh traces per figure, so "
                          "that a trace's per-kernel average x launches reproduces the figure")
@@ -470,9 +473,10 @@ def main():
                     help="N = 1: replay the step as one hipGraph (measured r04: 1073.3 vs 1073.4 TFLOP/s stream-ordered -- the "
                          "queue never runs dry, so this is not the default)")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="roofline.traffic from the committed PMC constant instead of rocprofv3 child passes in this run (~40 s)")
+                    help="--full: roofline.traffic from the committed PMC constant instead of rocprofv3 child passes in this run "
+                         "(~40 s)")
     ap.add_argument("--no-decode-pipeline", action="store_true",
-                    help="N > 1: skip the bounded configs[2] side figure (greedy decode through the layer pipeline)")
+                    help="--full, N > 1: skip the bounded configs[2] side figure (greedy decode through the layer pipeline)")
     ap.add_argument("--fuse", action="store_true",
                     help="NOT the headline configuration: q|k|v and gate|up as one launch each (5 launches per layer "
                          "instead of 7; same weights, same FLOPs), reported with config.fused_launches = true")
@@ -657,8 +661,8 @@ def main():
     if world == 1 and tpath:
         traffic = json.load(open(tpath))["avg_hbm_bytes_per_launch"]
 
-    # N > 1: who took part (all-reduce of ones + every rank's device identity), and a bounded BASELINE configs[2] figure:
-    # 32 greedy-decode tokens through the same layer pipeline, rank 0 re-decoding them in one process to compare the ids.
+    # N > 1: who took part (all-reduce of ones + every rank's device identity), and with --full a bounded BASELINE configs[2]
+    # figure: 32 greedy-decode tokens through the same layer pipeline, rank 0 re-decoding them in one process to compare the ids.
     # After the timed region; every rank runs it.
     census = rank_census(dev) if world > 1 else None
     if census is not None and backend == "nccl" and (census["ranks_seen"] != world or census["distinct_devices"] != world):
@@ -669,12 +673,13 @@ def main():
                   f"{census['ranks_seen']} distinct_devices={census['distinct_devices']}: {census['ranks']}", file=sys.stderr, flush=True)
         raise SystemExit(3)
     decode_fig = None
-    if world > 1 and rank == 0:
+    decode_figure = world > 1 and args.full and not args.no_decode_pipeline
+    if decode_figure and rank == 0:
         # the headline of this run, on stderr, BEFORE the side figure: should the decode pipeline fail on hardware it has never
         # seen, the record still holds what the timed region measured (stdout carries the one complete line at the end)
         pipeline.rank_log("headline so far: " + json.dumps({"value_TFLOPs": round(value, 3), "n_gpus": world, "steps": args.steps,
                                                             "ms_per_step": round(ms_per_step, 4), "per_rank": per_rank}), rank, world)
-    if world > 1 and not args.no_decode_pipeline:
+    if decode_figure:
         phase("decode pipeline figure", 240)
         from mxq_amd.llama_decode import decode_pipeline_figure
         decode_fig = decode_pipeline_figure(pipe, dev, tokens=32, ctx=64, verify=True, dist=dist, backend=backend)
@@ -716,7 +721,7 @@ def main():
                          "frac_at_held_clock": (round(achieved / (PEAK_F16_TFLOPS * sclk["median"] / 2400.0), 4)
                                                 if sclk and sclk["median"] > 0 else None)},
         }
-        if world == 1 and not args.headline_only and not args.no_live_traffic:
+        if world == 1 and args.full and not args.no_live_traffic:
             lt = live_traffic()
             if lt is not None:
                 out["roofline"]["traffic"] = lt[0]
@@ -734,13 +739,13 @@ def main():
         if decode_fig is not None:
             decode_fig.pop("token_ids", None)
             out["decode_pipeline"] = decode_fig
-        if world == 1 and not args.fuse and not args.headline_only:
+        if world == 1 and args.full and not args.fuse:
             out["fused_launches_figure"] = fused_launch_figure(layers, dev, x_h, x_i, y_h)
             # the other BASELINE configs, each with its own roofline fraction (side figures; `value` is configs[1])
             out["decode_1gpu"] = decode_1gpu(dev)              # configs[2] on one GPU (HBM-bound)
             out["fakequant_block"] = fakequant_block(dev)      # configs[3] (HBM-bound)
             out["config5"] = config5(dev)                      # configs[4] (MFMA-bound prefill leg, HBM-bound decode leg)
-        if world == 1 and not args.no_cpu_baseline and not args.headline_only:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(dev)
         print(json.dumps(out), flush=True)
     if dist is not None:

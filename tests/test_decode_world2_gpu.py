@@ -55,7 +55,7 @@ def test_bench_world2_proves_its_ranks_and_carries_the_decode_figure():
     (32 greedy-decode tokens through the same layer pipeline, rank 0 re-decoding them in one process).  On the driver's
     8-GPU SCALE run the same fields read ranks_seen = distinct_devices = N over RCCL."""
     env = dict(os.environ, MXQ_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = _torchrun(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1"], env, 900)
+    r = _torchrun(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--full"], env, 900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 2 and d["ranks_seen"] == 2 and d["backend"] == "gloo"
@@ -96,7 +96,7 @@ def test_bench_world4_rehearsal_on_one_gpu():
     rehearsed on CPU by tests/test_pipeline_gloo.py through the same harness objects): 8 layers per rank, 4 sequences in
     flight, every rank's report on the line."""
     env = dict(os.environ, MXQ_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = _torchrun(4, [os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "1", "--warmup", "1"], env, 600)
+    r = _torchrun(4, [os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "1", "--warmup", "1", "--full"], env, 600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 4 and d["ranks_seen"] == 4 and d["backend"] == "gloo" and d["distinct_devices"] == 1

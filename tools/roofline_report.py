@@ -34,7 +34,7 @@ def last_json(text):
 
 def main():
     rep = {"peaks": {"fp16_mfma_TFLOPs": 2500.0, "hbm_GBps_spec": 8000.0, "hbm_GBps_achievable": 6300.0}}
-    b = last_json(run(["bench.py", "--gpus", "1", "--steps", "10", "--warmup", "3"]))
+    b = last_json(run(["bench.py", "--gpus", "1", "--steps", "10", "--warmup", "3", "--full"]))
     rep["config1_cpu_dequant_linear"] = b["cpu_baseline"]
     rep["config2_prefill_all_linears"] = {k: b[k] for k in ("value", "unit", "ms_per_step", "tokens_per_s", "roofline")}
     rep["config3_decode_1gpu"] = {}
