@@ -228,6 +228,25 @@ int mxq_linear_f16_auto(const void* x, const void* qweight, const void* rowmeta,
  * kernel explicitly (2 -> MXQ_E_SHAPE if K % 128 != 0).  Both kernels give bit-identical results. */
 int mxq_dense_f16(const void* x, const void* w16, void* y, int M, int N, int K, int variant, void* stream);
 
+/* Input gradient of the quantised Linear (backpropagation through a packed layer; csrc/gemm_dx.hip):
+ * dx[M, K] = dy[M, N] . W'[N, K], W' the bit-exact dequantised weight (what mxq_dequant_f16 / mxq_dequant_f16_compact
+ * write), dy and dx fp16 row-major and contiguous, fp32 accumulation, fp16 result (RNE).  layout MXQ_LAYOUT_MIXED or
+ * MXQ_LAYOUT_MIXEDC.  `workspace` NULL: one launch of whole 128 x 256 tiles, each walking the whole N reduction.  With a
+ * workspace of at least mxq_linear_grad_input_workspace_need(M, N, K, layout) bytes (16-byte aligned, e.g. the GEMM
+ * workspace) the N reduction is split into S slices where the tiles alone do not fill the chip: fp32 partial slabs beyond
+ * the head (MXQ_WS_HEAD_BYTES; the head itself is never read or written), summed in slice order by a second launch.
+ * Run-to-run deterministic.  MXQ_E_NULL for a missing operand; MXQ_E_SHAPE for M <= 0, N % 16, K % 64, another layout or
+ * a too small workspace; MXQ_E_ALIGN for a pointer that is not 16-byte aligned.  need is 0 where the schedule is one
+ * launch, else MXQ_WS_HEAD_BYTES + S * M * K * 4 <= mxq_gemm_workspace_bytes(); 0 for rejected arguments.  Host-only. */
+int mxq_linear_grad_input_f16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                              int layout, void* workspace, size_t workspace_bytes, void* stream);
+size_t mxq_linear_grad_input_workspace_need(int M, int N, int K, int layout);
+/* ... with an explicit number of N slices (1..64; 1: one launch, no workspace needed; else a workspace of at least
+ * MXQ_WS_HEAD_BYTES + slices * M * K * 4 bytes): the schedules by name, for tests and tools. */
+int mxq_linear_grad_input_f16_sliced(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N,
+                                     int K, int layout, int slices, void* workspace, size_t workspace_bytes,
+                                     void* stream);
+
 /* Uniform-bit-width layouts for the W2A16 / W4A16 / mixed sweep (BASELINE config 5); the mixed
  * layout is layout 0.  1 = W2G16: Quantizer(bits=2, qq_scale_bits=4) on every 16-column group
  * (quantizer.py:61-147), 4.5 bit/weight; 2 = W4ROW: Quantizer(bits=4, qq_scale_bits=4) per row

@@ -60,6 +60,10 @@ SIGNATURES = {
     "mxq_linear_f16_auto": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t,
                                     c_void_p]),
     "mxq_dense_f16": (c_int, [c_void_p] * 3 + [c_int, c_int, c_int, c_int, c_void_p]),
+    "mxq_linear_grad_input_f16": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "mxq_linear_grad_input_workspace_need": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "mxq_linear_grad_input_f16_sliced": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                                                                 c_void_p]),
     "mxq_linear_f16_ws": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "mxq_linear_f16_layout_ws": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "mxq_gemm_f16_ws": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),

@@ -449,6 +449,50 @@ size_t mxq_linear_workspace_need(int M, int N, int K, int layout, int hoisting) 
 
 int mxq_hoist_min_tokens(void) { return HOIST_MIN_TOKENS; }
 
+// input gradient of the quantised Linear (csrc/gemm_dx.hip): arguments checked in the order of the Linear family
+// (NULL, then shapes and the workspace's size, then alignment); `slab_need` is the workspace the schedule needs (0: none)
+namespace {
+size_t grad_input_slab_bytes(size_t workspace_bytes) {
+    return workspace_bytes > MXQ_WS_HEAD_BYTES ? workspace_bytes - MXQ_WS_HEAD_BYTES : 0;
+}
+int grad_input_check(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K, int layout,
+                     const void* workspace, size_t workspace_bytes, size_t ws_need) {
+    if (!dy || !qweight || !rowmeta || !dx) return MXQ_E_NULL;
+    if (!shape_ok(N, K) || M <= 0 || !mxq_layout_is_mixed(layout)) return MXQ_E_SHAPE;
+    if (workspace && workspace_bytes < ws_need) return MXQ_E_SHAPE;
+    if (!aligned16(dy) || !aligned16(qweight) || !aligned16(rowmeta) || !aligned16(dx)) return MXQ_E_ALIGN;
+    if (workspace && !aligned16(workspace)) return MXQ_E_ALIGN;
+    return 0;
+}
+}   // namespace
+
+size_t mxq_linear_grad_input_workspace_need(int M, int N, int K, int layout) {
+    if (!shape_ok(N, K) || M <= 0 || !mxq_layout_is_mixed(layout)) return 0;
+    const int S = mxq_gemm_dx_slices(M, N, K, grad_input_slab_bytes(mxq_gemm8_workspace_bytes()));
+    return S > 1 ? MXQ_WS_HEAD_BYTES + (size_t)S * M * K * 4 : 0;
+}
+
+int mxq_linear_grad_input_f16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                              int layout, void* workspace, size_t workspace_bytes, void* stream) {
+    const size_t need = mxq_linear_grad_input_workspace_need(M, N, K, layout);
+    if (const int e = grad_input_check(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, need)) return e;
+    const int S = workspace ? mxq_gemm_dx_slices(M, N, K, grad_input_slab_bytes(workspace_bytes)) : 1;
+    return mxq_launch_gemm_dx_f16(dy, qweight, rowmeta, dx, M, N, K, layout,
+                                  S > 1 ? (char*)workspace + MXQ_WS_HEAD_BYTES : nullptr, S, (hipStream_t)stream);
+}
+
+int mxq_linear_grad_input_f16_sliced(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N,
+                                     int K, int layout, int slices, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    if (slices > 1 && !workspace) return MXQ_E_NULL;
+    const size_t need = slices > 1 && M > 0 && K > 0 ? MXQ_WS_HEAD_BYTES + (size_t)slices * M * K * 4 : 0;
+    if (const int e = grad_input_check(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, need)) return e;
+    if (slices < 1 || slices > 64) return MXQ_E_SHAPE;
+    return mxq_launch_gemm_dx_f16(dy, qweight, rowmeta, dx, M, N, K, layout,
+                                  slices > 1 ? (char*)workspace + MXQ_WS_HEAD_BYTES : nullptr, slices,
+                                  (hipStream_t)stream);
+}
+
 // hipStreamGetCaptureInfo through THIS library's HIP runtime (the process's own: a caller that dlopens "libamdhip64.so" by
 // name may load a second runtime next to the one its framework bundles): *active = 1 and *id = the capture sequence's
 // id while `stream` is being captured, else *active = 0.

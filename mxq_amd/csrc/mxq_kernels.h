@@ -174,3 +174,8 @@ int mxq_launch_gemv_proto_f16(const void* x, const void* weight, const void* wei
                               const void* zeros_and_scales, const void* scales_2nd, const void* zeros_2nd,
                               const void* scales_4b, const void* zeros_4b, void* y, int B, int IC, int OC,
                               hipStream_t stream);
+// gemm_dx.hip: the quantised Linear's input gradient (mixed layout, exact or compact metadata); `slices` <= 1: one launch
+// of whole tiles, else `slices` N-slices into fp32 slabs at `slab` (slices * M * K * 4 bytes) and a combine launch
+int mxq_gemm_dx_slices(int M, int N, int K, size_t slab_bytes);
+int mxq_launch_gemm_dx_f16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                           int layout, void* slab, int slices, hipStream_t stream);

@@ -513,6 +513,67 @@ def linear(x: torch.Tensor, p, out: Optional[torch.Tensor] = None, path: str = "
     return out.reshape(*x.shape[:-1], p.N)
 
 
+GRAD_INPUT_PATHS = ("auto", "single", "slices")
+
+
+def grad_input_slices(M: int, N: int, K: int) -> int:
+    """The number of N slices the "slices" path of ``linear_grad_input`` runs: the auto schedule's where it slices, else
+    2 .. 4 (as many as fit the workspace; 1 where not even 2 fit)."""
+    lib = _lib.load()
+    need = lib.mxq_linear_grad_input_workspace_need(M, N, K, 0)
+    if need:
+        return (need - _lib.WS_HEAD_BYTES) // (M * K * 4)
+    fit = (lib.mxq_gemm_workspace_bytes() - _lib.WS_HEAD_BYTES) // (M * K * 4)
+    return max(1, min(4, fit))
+
+
+def linear_grad_input(dy: torch.Tensor, p: PackedMXQ, out: Optional[torch.Tensor] = None, path: str = "auto") -> torch.Tensor:
+    """dx = dy @ W for dy [..., N] fp16 -> [..., K] fp16 (fp32 accumulation), W the dequantised weight of a PackedMXQ
+    (exact or compact metadata): the input gradient of ``linear``, computed by the fused dequant kernel without
+    materialising W (include/mxq_hip.h: mxq_linear_grad_input_f16).
+
+    path: "auto" (the library's schedule, with a workspace sized by mxq_linear_grad_input_workspace_need), "single" (one
+    launch of whole tiles, no workspace), "slices" (the N reduction split into ``grad_input_slices`` slices: tests)."""
+    if not isinstance(p, PackedMXQ):
+        raise ValueError("linear_grad_input needs a PackedMXQ weight (mixed layout, exact or compact metadata)")
+    _need_gpu(dy, p.qweight)
+    if dy.dtype != torch.float16:
+        raise ValueError(f"gradients must be float16, got {dy.dtype}")
+    if dy.dim() < 1 or dy.shape[-1] != p.N:
+        raise ValueError(f"out_features mismatch: dy has {dy.shape[-1] if dy.dim() else None}, weight has {p.N}")
+    if dy.device != p.qweight.device:
+        raise ValueError("dy and the packed weight live on different devices")
+    if path not in GRAD_INPUT_PATHS:
+        raise ValueError(f"unknown path {path!r}")
+    dy2 = dy.reshape(-1, p.N).contiguous()
+    M = dy2.shape[0]
+    if out is None:
+        out = torch.empty((M, p.K), dtype=torch.float16, device=dy.device)
+    elif out.shape != (M, p.K) or out.dtype != torch.float16 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float16 [tokens, in_features] tensor")
+    if M == 0:
+        return out.reshape(*dy.shape[:-1], p.K)
+    lib = _lib.load()
+    lay = _layout_code(p)
+    args = (dy2.data_ptr(), p.qweight.data_ptr(), p.rowmeta.data_ptr(), out.data_ptr(), M, p.N, p.K, lay)
+    st = _stream(dy2)
+    with _on_device(dy.device):
+        if path == "auto":
+            ws = gemm_workspace(dy2.device, counters=False, stream=st,
+                                need=lib.mxq_linear_grad_input_workspace_need(M, p.N, p.K, lay))
+            rc = lib.mxq_linear_grad_input_f16(*args, ws.data_ptr() if ws is not None else None,
+                                               ws.numel() if ws is not None else 0, st)
+        else:
+            S = 1 if path == "single" else grad_input_slices(M, p.N, p.K)
+            if path == "slices" and S < 2:
+                raise ValueError(f"the slices of {M} tokens x {p.K} columns do not fit the workspace")
+            ws = gemm_workspace(dy2.device, counters=False, stream=st) if S > 1 else None
+            rc = lib.mxq_linear_grad_input_f16_sliced(*args, S, ws.data_ptr() if ws is not None else None,
+                                                      ws.numel() if ws is not None else 0, st)
+        _lib.check(rc, f"linear_grad_input[{path}]")
+    return out.reshape(*dy.shape[:-1], p.K)
+
+
 def linear_layout(x: torch.Tensor, p, out: Optional[torch.Tensor] = None, path: str = "gemm") -> torch.Tensor:
     """The former layout entry, kept as a name for bench.py: `linear` with its old default path "gemm"."""
     return linear(x, p, out=out, path=path)

@@ -20,6 +20,22 @@ import torch.nn as nn
 from . import packing
 
 
+class _QuantLinearFn(torch.autograd.Function):
+    """y = x W^T through the packed weight, differentiable in x alone: the forward is exactly ``packing.linear``, the
+    backward dx = dy W runs the fused dequant kernel (packing.linear_grad_input).  No activation is saved -- dx needs the
+    packed weight only -- and the weight's buffers get no gradient (frozen packed base)."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, mod: "QuantLinear") -> torch.Tensor:
+        ctx.mod = mod
+        return packing.linear(x, mod.packed())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy: torch.Tensor):
+        return packing.linear_grad_input(dy, ctx.mod.packed()), None
+
+
 class QuantLinear(nn.Module):
     def __init__(self, in_features: int, out_features: int, bias: bool = False, device=None, compact: bool = False,
                  _buffers=None):
@@ -79,7 +95,10 @@ class QuantLinear(nn.Module):
         return packing.dequant(self.packed())
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        y = packing.linear(x, self.packed())
+        if torch.is_grad_enabled() and x.requires_grad:
+            y = _QuantLinearFn.apply(x, self)
+        else:
+            y = packing.linear(x, self.packed())
         if self.bias is not None:
             y = y + self.bias
         return y
