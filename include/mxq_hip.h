@@ -20,10 +20,10 @@
  *     reported one at launch, or a negative MXQ_E* code for rejected arguments;
  *   - nothing here allocates or frees device memory, and nothing synchronises except mxq_workspace_status: outputs
  *     and scratch are caller-allocated and the library is re-entrant (safe under hipGraph capture).  The library keeps
- *     exactly two pieces of process-global HOST state, both caches of device facts that never change: the CU count of
- *     the first device a stream-K launcher ran on (csrc/gemm8.hip cu_count(): one device model per process is assumed),
- *     and one bit per (kernel, device ordinal) recording that hipFuncSetAttribute(MaxDynamicSharedMemorySize) was made
- *     (csrc/mxq_kernels.h mxq_set_dyn_lds_once).  No data-dependent state survives a call;
+ *     process-global HOST state only as caches of device facts that never change, kept per device ordinal in
+ *     csrc/mxq_kernels.h: the CU count (mxq_cu_count), a kernel's resident workgroups (mxq_resident_workgroups) and one
+ *     bit per kernel recording that hipFuncSetAttribute(MaxDynamicSharedMemorySize) was made (mxq_set_dyn_lds_once).
+ *     No data-dependent state survives a call;
  *   - shapes: weight W[N, K] row-major (nn.Linear.weight), N % 16 == 0, K % 64 == 0.
  */
 #ifndef MXQ_HIP_H

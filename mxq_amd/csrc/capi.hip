@@ -653,12 +653,14 @@ int mxq_gemm_awq_f16(const void* x, const void* kernel, const void* scales, cons
         const int e = mxq_launch_skinny_awq_f16(x, kernel, scales, zeros, y, M, IC, OC, group_size, workspace, workspace_bytes, st);
         if (e != MXQ_NOT_MY_SHAPE) return e;
     }
-    if (M <= 64 && workspace && workspace_bytes >= mxq_gemm8aq_workspace_bytes() && tn <= 176)
-        return mxq_launch_gemm8aq_f16(x, kernel, scales, zeros, y, M, IC, OC, group_size, workspace, workspace_bytes, tn <= 64 ? -1 : -2, st);
+    if (M <= 64 && workspace && workspace_bytes >= mxq_gemm8aq_workspace_bytes() && tn <= STREAMK_MAX_TILES)
+        return mxq_launch_gemm8aq_f16(x, kernel, scales, zeros, y, M, IC, OC, group_size, workspace, workspace_bytes,
+                                      tn <= SLICES_MAX_TILES ? -1 : -2, st);
     if (M <= 64 && !workspace) return mxq_launch_gemm8aq_f16(x, kernel, scales, zeros, y, M, IC, OC, group_size, nullptr, 0, 0, st);
     const int t128 = ((M + 127) / 128) * tn;
-    if (M <= 1024 && workspace && workspace_bytes >= mxq_gemm8ah_workspace_bytes() && t128 <= 176)
-        return mxq_launch_gemm8ah_f16(x, kernel, scales, zeros, y, M, IC, OC, group_size, workspace, workspace_bytes, t128 <= 64 ? -1 : -2, st);
+    if (M <= 1024 && workspace && workspace_bytes >= mxq_gemm8ah_workspace_bytes() && t128 <= STREAMK_MAX_TILES)
+        return mxq_launch_gemm8ah_f16(x, kernel, scales, zeros, y, M, IC, OC, group_size, workspace, workspace_bytes,
+                                      t128 <= SLICES_MAX_TILES ? -1 : -2, st);
     return mxq_launch_gemm8a_f16(x, kernel, scales, zeros, y, M, IC, OC, group_size, workspace, workspace_bytes, 0, st);
 }
 

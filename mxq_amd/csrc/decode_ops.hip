@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "mxq_amdgcn.h"
 #include "mxq_kernels.h"
 
 #include "mxq_gemv_common.h"   // wave_allsum / wave_allmax / quad_allsum: the shuffle butterflies as vector-ALU operations, bit-identical
@@ -14,12 +15,6 @@ namespace {
 
 constexpr int HD = 128;        // head dim (Llama-2-7B)
 constexpr int ATT_THREADS = 256;
-
-__device__ __forceinline__ float h2f(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
-__device__ __forceinline__ uint16_t f2h(float f) {
-    const _Float16 h = (_Float16)f;
-    return __builtin_bit_cast(uint16_t, h);
-}
 
 // qkv: [3 * heads * HD] fp16 (q | k | v); caches: [heads][max_ctx][HD] fp16; cos/sin: [max_ctx][HD/2] f32;
 // out: [heads * HD] fp16.  Rotate-half convention, as mxq_amd/llama_decode.py.
@@ -382,8 +377,7 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_split_kernel(const ui
     // together (agent-scope: sc1 buffer loads; clamped to the last part, whose weight is then zero) -- read one after the
     // other, 16 parts were 16 dependent round trips, most of the launch at 2000 keys
     if (tid < HD) {
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(part + (int64_t)h * S * (HD + 2)), 0,
-                                                                           S * (HD + 2) * 4, 0x00020000);
+        const rsrc_t rs = make_rsrc(part + (int64_t)h * S * (HD + 2), S * (HD + 2) * 4);
         float m_[MAX_SPLITS], l_[MAX_SPLITS], o_[MAX_SPLITS];
 #pragma unroll
         for (int s2 = 0; s2 < MAX_SPLITS; ++s2) {
@@ -561,16 +555,25 @@ int mxq_launch_lmhead_argmax_f16(const void* h, const void* norm_w, float eps, c
     return (int)hipGetLastError();
 }
 
+// dynamic LDS of an attention workgroup: q, knew, vnew [HD], scores [max_ctx], red [8], o2 [16 * HD], fp32
+static size_t attn_smem(int max_ctx) { return (size_t)(3 * HD + max_ctx + 8 + 16 * HD) * 4; }
+
+// beyond 64 KiB the kernel needs the ceiling raised: set once per kernel and device to the CU's whole LDS, which bounds
+// every max_ctx (a larger request fails here, before the launch)
+template <auto Kernel>
+static hipError_t attn_lds_ceiling(size_t smem) {
+    if (smem <= 64 * 1024) return hipSuccess;
+    if (smem > 160 * 1024) return hipErrorInvalidValue;
+    return mxq_set_dyn_lds_once<Kernel>(160 * 1024);
+}
+
 template <bool ROW>
 static int launch_attn(const void* qkv, void* k_cache, void* v_cache, const void* pos, const void* cos_t, const void* sin_t,
                        void* out, int heads, int head_dim, int max_ctx, hipStream_t stream) {
     if (head_dim != HD) return (int)hipErrorInvalidValue;
-    const size_t smem = (size_t)(3 * HD + max_ctx + 8 + 16 * HD) * 4;
-    if (smem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_decode_kernel<ROW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)smem);
-        if (e != hipSuccess) return (int)e;
-    }
+    const size_t smem = attn_smem(max_ctx);
+    hipError_t e = attn_lds_ceiling<&attn_decode_kernel<ROW>>(smem);
+    if (e != hipSuccess) return (int)e;
     attn_decode_kernel<ROW><<<heads, ATT_THREADS, smem, stream>>>((const uint16_t*)qkv, (uint16_t*)k_cache,
                                                                   (uint16_t*)v_cache, (const int64_t*)pos,
                                                                   (const float*)cos_t, (const float*)sin_t, (uint16_t*)out,
@@ -592,12 +595,9 @@ size_t mxq_attn_split_workspace_bytes_impl(int heads, int splits) {
 int mxq_launch_attn_decode_split_f16(const void* qkv, void* k_cache, void* v_cache, const void* pos, const void* rope_row,
                                      void* out, int heads, int head_dim, int max_ctx, int splits, void* ws, hipStream_t stream) {
     if (head_dim != HD || splits > MAX_SPLITS) return (int)hipErrorInvalidValue;
-    const size_t smem = (size_t)(3 * HD + max_ctx + 8 + 16 * HD) * 4;
-    if (smem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)attn_decode_split_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)smem);
-        if (e != hipSuccess) return (int)e;
-    }
+    const size_t smem = attn_smem(max_ctx);
+    hipError_t e = attn_lds_ceiling<&attn_decode_split_kernel<true>>(smem);
+    if (e != hipSuccess) return (int)e;
     int* cnt = (int*)ws;
     float* part = (float*)((char*)ws + (size_t)((heads + 255) / 256) * 1024);
     attn_decode_split_kernel<true><<<heads * splits, ATT_THREADS, smem, stream>>>(

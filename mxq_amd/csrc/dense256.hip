@@ -24,15 +24,11 @@
 // (the last phases of a tile stage the next tile's first units), so the pipeline never drains.
 #include <hip/hip_runtime.h>
 
+#include "mxq_amdgcn.h"
 #include "mxq_dequant.h"
 #include "mxq_kernels.h"
 
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
 
 constexpr int BM = 256, BN = 256, BK = 64, THREADS = 512;
 constexpr int UNIT = 128 * BK * 2;      // 16 KB: 128 rows x 64 k fp16
@@ -40,16 +36,6 @@ constexpr int SMEM = 8 * UNIT;          // 128 KB
 enum { UA = 0, UB = 1, UC = 2, UD = 3 };
 
 #define D256_FENCE() __builtin_amdgcn_sched_barrier(0)
-
-#define D256_LANE_ID(v) asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(v))
-
-__device__ __forceinline__ int swz(int row, int slot) { return row * 128 + ((slot ^ (row & 7)) << 4); }
-__device__ __forceinline__ void bufdma16(rsrc_t rsrc, uint32_t voff, uint32_t soff, void* l) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)l, 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ rsrc_t make_rsrc(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, 0x00020000);
-}
 
 // Tile order (speed only): XCD e (= tile index & 7) owns a band of token-tile rows and walks it in blocks of 4 x-tiles
 // against 8 weight tiles, so that the 32 workgroups of an XCD share operands in its L2; needs tiles_m % 32 == 0,
@@ -230,7 +216,7 @@ __global__ __launch_bounds__(THREADS) void mxq_dense256_f16_kernel(const uint16_
     const int NT = K / BK;           // even, >= 2 (launcher)
     const int wr = wave >> 2, wc = wave & 3;
     int ln;
-    D256_LANE_ID(ln);
+    MXQ_LANE_ID(ln);
     // per-lane source offsets of the wave's two pieces of each unit kind: piece pc = 2 wave + h holds the unit's rows
     // 8 pc .. 8 pc + 7, a lane's 16 bytes = k-slot (lane & 7) ^ (row & 7) of row (lane >> 3)   [XOR swizzle on the source side]
     uint32_t voff[4][2];
@@ -262,11 +248,11 @@ __global__ __launch_bounds__(THREADS) void mxq_dense256_f16_kernel(const uint16_
     if (wr) __builtin_amdgcn_s_barrier();              // group 1 runs one barrier interval behind group 0
     Regs R;
     {
-        D256_LANE_ID(ln);
+        MXQ_LANE_ID(ln);
         load_w<SEQ_B>(smem, 1, wc, ln & 15, ln >> 4, R.w0[0]);   // "phase -1": the first K-tile's first weight sub-tile
     }
     for (int tile = blockIdx.x; tile < tiles; tile += grid) {
-        D256_LANE_ID(ln);
+        MXQ_LANE_ID(ln);
         const int fr = ln & 15, fq = ln >> 4;
         const int m0 = tm * BM, n0 = tn * BN;
         const bool more = tile + grid < tiles;
@@ -285,19 +271,6 @@ __global__ __launch_bounds__(THREADS) void mxq_dense256_f16_kernel(const uint16_
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last (empty-descriptor) pieces still write zeros into this LDS
 }
 
-int cu_count8() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n >= 8)
-            cus = n / 8 * 8;
-        else
-            cus = 256;
-    }
-    return cus;
-}
-
 }   // namespace
 
 // -> 0 launched; MXQ_NOT_MY_SHAPE: the shape is not this kernel's (K-tile count odd or < 2, rows beyond the 32-bit descriptor offsets, or
@@ -305,7 +278,7 @@ int cu_count8() {
 int mxq_launch_dense256_f16(const void* x, const void* w16, void* y, int M, int N, int K, int force, hipStream_t stream) {
     if (K % (2 * BK) != 0 || K < 2 * BK || (int64_t)BM * K * 2 >= ((int64_t)1 << 32)) return MXQ_NOT_MY_SHAPE;
     const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN, tiles = tiles_m * tiles_n;
-    const int cus = cu_count8();
+    const int cus = mxq_cu_count() / 8 * 8;   // whole XCDs (tile_of)
     if (!force) {
         // Take this kernel when its ~17 % per-flop advantage (profiles/r03_dense256.txt) outweighs the coarser tile
         // quantisation: share of the launch's (rounds x CUs) tile slots that hold a tile, here and for 256 x 128 tiles.
@@ -314,7 +287,7 @@ int mxq_launch_dense256_f16(const void* x, const void* w16, void* y, int M, int 
         const double e128 = (double)t128 / ((double)((t128 + cus - 1) / cus) * cus);
         if (1.17 * e256 < e128) return MXQ_NOT_MY_SHAPE;
     }
-    hipError_t e = hipFuncSetAttribute((const void*)mxq_dense256_f16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
+    hipError_t e = mxq_set_dyn_lds_once<&mxq_dense256_f16_kernel>(SMEM);
     if (e != hipSuccess) return (int)e;
     const int grid = tiles < cus ? tiles : cus;
     mxq_dense256_f16_kernel<<<grid, THREADS, SMEM, stream>>>((const uint16_t*)x, (const uint16_t*)w16, (uint16_t*)y, M, N, K,

@@ -20,24 +20,18 @@
 //   * two LDS buffers; loads for step t+1 are issued before the MFMAs of step t.
 #include <hip/hip_runtime.h>
 
+#include "mxq_amdgcn.h"
 #include "mxq_dequant.h"
 #include "mxq_format.h"
 #include "mxq_kernels.h"
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int A_BYTES = BM * BK * 2;   // 16 KiB
 constexpr int B_BYTES = BN * BK * 2;   // 16 KiB
 constexpr int STAGE_BYTES = A_BYTES + B_BYTES;
 constexpr int SMEM_BYTES = 2 * STAGE_BYTES;   // 64 KiB -> 2 workgroups per CU
-
-// byte offset of 16-B slot `slot` (0..7) of row `row` in a [rows][64 halfs] tile
-__device__ __forceinline__ int swz(int row, int slot) { return row * 128 + ((slot ^ (row & 7)) << 4); }
 
 // packed operands of one thread for one K-step (qp 0: groups 0,1; qp 1: group 2 + 4-bit arm)
 struct BStage {
@@ -211,8 +205,7 @@ int mxq_launch_gemm_f16(const void* x, const void* qweight, const void* rowmeta,
 
 int mxq_launch_gemm1_f16(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
                          hipStream_t stream) {
-    hipError_t e = hipFuncSetAttribute((const void*)mxq_gemm_f16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       SMEM_BYTES);
+    hipError_t e = mxq_set_dyn_lds_once<&mxq_gemm_f16_kernel>(SMEM_BYTES);
     if (e != hipSuccess) return (int)e;
     const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
     mxq_gemm_f16_kernel<<<tiles_m * tiles_n, 256, SMEM_BYTES, stream>>>(

@@ -46,18 +46,12 @@
 #include <type_traits>
 
 #include "../../include/mxq_hip.h"
+#include "mxq_amdgcn.h"
 #include "mxq_dequant.h"
 #include "mxq_format.h"
 #include "mxq_kernels.h"
 
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 // The token height of the tile is a build parameter: this file is compiled twice.  gemm8.hip itself: 256 tokens, 8 MFMA
 // waves (2 per SIMD) -- the prefill kernel.  gemm8h.hip (#defines MXQ_G8_BM 128 and includes this file): 128 tokens, 4 MFMA
@@ -188,18 +182,6 @@ constexpr int SK_STAMP_OFF = 32768;   // bytes: the stamps' area in the workspac
 // parked pieces and every wait gives up after 4096 polls -- the launch must end with the workspace's status words set and
 // the starved tiles poisoned, not with silently wrong sums
 [[maybe_unused]] constexpr int EXP_SK_WITHHOLD = 65536;
-
-__device__ __forceinline__ int swz(int row, int slot) { return row * 128 + ((slot ^ (row & 7)) << 4); }
-
-// LDS-DMA through a buffer descriptor: 16 B per lane, LDS destination = wave-uniform base + 16 * lane;
-// global source = descriptor base + voff (per lane) + soff (scalar); out-of-range sources deliver zeros
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-__device__ __forceinline__ void bufdma16(rsrc_t rsrc, uint32_t voff, uint32_t soff, void* l) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)l, 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ rsrc_t make_rsrc(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, 0x00020000);
-}
 
 // XCD-aware tile order (speed only): tiles are dealt to the 8 XCDs as compact 2-D blocks (4 x 2 regions)
 __device__ __forceinline__ void tile_of_block(int bid, int tiles_m, int tiles_n, int& tm, int& tn) {
@@ -1385,8 +1367,6 @@ __device__ __forceinline__ void wdma_segment(const WDma& w, char* smem, bool pre
     next();
 }
 
-#define MXQ_LANE_ID(ln) asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln))
-
 // grid = max(dp_grid, 8 * units) persistent workgroups: the first dp_grid deal the first dp_tiles tiles round-robin
 // (tile = block + k * dp_grid: blocks b and b + 8 share an XCD and dp_grid is a multiple of 8 or the tile count itself, so a
 // workgroup's tiles keep its XCD's label) and overlap one tile's output with the next one's first DMAs; the first
@@ -1659,31 +1639,20 @@ __global__ __launch_bounds__(256) void G8_SYM(, _combine_kernel)(const float* __
     store_block_xpose(c4, y, M, N, tm * BM, tn * BN, ws / WGN, ws % WGN, jj, lane & 15, lane >> 4);
 }
 
-int cu_count() {
-    static int cus = 0;   // one device model per process on this platform
-    if (!cus) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-            cus = n;
-        else
-            cus = 256;
-    }
-    return cus;
+// the DMA descriptors address with 32-bit offsets: BM rows of x per descriptor; the whole packed weight behind one (< 2^31)
+bool offsets_fit(int N, int K) {
+    return (int64_t)BM * K * 2 < ((int64_t)1 << 32) && (int64_t)(N / 16) * (K / BK) * MXQ_BLK_BYTES < ((int64_t)1 << 31);
 }
 
 template <int ABL, int LAYOUT = MXQ_LAYOUT_MIXED>
 static int launch8(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
                    void* workspace, size_t ws_bytes, bool force, hipStream_t stream G8_AWQ_PARAM) {
-    // the DMA descriptors address one tile's rows with 32-bit offsets: 256 rows of x, 8 row-blocks of packed weights
-    // 32-bit offsets: 256 rows of x per DMA descriptor; the whole packed weight behind one (offsets < 2^31)
-    if ((int64_t)BM * K * 2 >= ((int64_t)1 << 32) || (int64_t)(N / 16) * (K / BK) * MXQ_BLK_BYTES >= ((int64_t)1 << 31))
-        return -1;   // MXQ_E_SHAPE
+    if (!offsets_fit(N, K)) return MXQ_E_SHAPE;
     hipError_t e = mxq_set_dyn_lds_once<&G8_KERNEL<ABL, LAYOUT>>(SMEM_BYTES);
     if (e != hipSuccess) return (int)e;
     const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN, tiles = tiles_m * tiles_n;
     const int NT = K / BK;
-    const int cus = cu_count() / 8 * 8;
+    const int cus = mxq_cu_count() / 8 * 8;   // whole XCDs
     int units = cus / 8;
     int dp_tiles = tiles, tail = 0;
     // a stream-K launch's workgroups wait for one another: its grid (<= cus) must fit the device all at once -- asked of the
@@ -1733,14 +1702,13 @@ template <int LAYOUT>
 static int launch8_slices(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
                           void* workspace, size_t ws_bytes, int S, hipStream_t stream G8_AWQ_PARAM) {
     const int NT = K / BK, tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN, tiles = tiles_m * tiles_n;
-    if (S <= 0) S = cu_count() / tiles;               // (2-3 x as many slices, i.e. 2-3 workgroups per CU: no faster, profiles/r05_smalltile_slices.txt)
+    if (S <= 0) S = mxq_cu_count() / tiles;           // (2-3 x as many slices, i.e. 2-3 workgroups per CU: no faster, profiles/r05_smalltile_slices.txt)
     if (S > NT / 4) S = NT / 4;                       // at least 4 K-steps per slice
     const size_t room = workspace && ws_bytes > MXQ_WS_HEAD_BYTES ? (ws_bytes - MXQ_WS_HEAD_BYTES) / ((size_t)tiles * BM * BN * sizeof(float)) : 0;
     if ((size_t)S > room) S = (int)room;
     if (S <= 1) return launch8<0, LAYOUT>(x, qweight, rowmeta, y, M, N, K, nullptr, 0, false, stream G8_AWQ_ARG);
-    if (M <= 0 || N <= 0 || K < BK || K % BK != 0 || N % (LAYOUT == LAYOUT_AWQ ? 8 : 16) != 0) return -1;
-    if ((int64_t)BM * K * 2 >= ((int64_t)1 << 32) || (int64_t)(N / 16) * (K / BK) * MXQ_BLK_BYTES >= ((int64_t)1 << 31))
-        return -1;
+    if (M <= 0 || N <= 0 || K < BK || K % BK != 0 || N % (LAYOUT == LAYOUT_AWQ ? 8 : 16) != 0) return MXQ_E_SHAPE;
+    if (!offsets_fit(N, K)) return MXQ_E_SHAPE;
     hipError_t e = mxq_set_dyn_lds_once<&G8_KERNEL<0, LAYOUT>>(SMEM_BYTES);
     if (e != hipSuccess) return (int)e;
     float* slab = (float*)((char*)workspace + MXQ_WS_HEAD_BYTES);
@@ -1753,17 +1721,19 @@ static int launch8_slices(const void* x, const void* qweight, const void* rowmet
 
 }   // namespace
 
+// the stream-K grid's workspace: the head, then two fp32 partial tiles per workgroup (one per CU of whole XCDs)
+size_t G8_SYM(, _workspace_bytes)() { return MXQ_WS_HEAD_BYTES + (size_t)(mxq_cu_count() / 8 * 8) * 2 * BM * BN * sizeof(float); }
+
 #ifdef MXQ_G8_AWQ
 // gemm_forward_cuda's operands (gemm_cuda.h:3-4): x fp16 [M, IC], kernel int32 [IC, OC / 8], scales fp16 [IC / G, OC], zeros int32
 // [IC / G, OC / 8] -> y fp16 [M, OC].  slices = 0: whole tiles + stream-K tail (workspace: counter head + partial slots, nullable);
 // slices > 0 (or -1: one workgroup per CU): every tile's K range cut that many ways + combine launch; -2: stream-K with the
 // tail always split (launches of few tiles).
-size_t G8_SYM(, _workspace_bytes)() { return MXQ_WS_HEAD_BYTES + (size_t)(cu_count() / 8 * 8) * 2 * BM * BN * sizeof(float); }
 int G8_SYM(launch_, _f16)(const void* x, const void* kernel, const void* scales, const void* zeros, void* y, int M, int IC, int OC,
                          int G, void* workspace, size_t ws_bytes, int slices, hipStream_t stream) {
     if (M <= 0 || IC < BK || IC % BK != 0 || OC <= 0 || OC % 8 != 0 || G < 8 || G % 8 != 0 || IC % G != 0 || G >= 4096 || IC >= (1 << 20))
-        return -1;   // MXQ_E_SHAPE
-    if ((int64_t)IC * OC / 2 >= ((int64_t)1 << 31) || (int64_t)(IC / G) * OC * 2 >= ((int64_t)1 << 31)) return -1;
+        return MXQ_E_SHAPE;
+    if ((int64_t)IC * OC / 2 >= ((int64_t)1 << 31) || (int64_t)(IC / G) * OC * 2 >= ((int64_t)1 << 31)) return MXQ_E_SHAPE;
     AwqOps awq;
     awq.scales = (const uint16_t*)scales;
     awq.zeros = (const uint32_t*)zeros;
@@ -1784,10 +1754,8 @@ int G8_SYM(launch_, _slices_f16)(const void* x, const void* qweight, const void*
         case MXQ_LAYOUT_W4ROW: return launch8_slices<MXQ_LAYOUT_W4ROW>(x, qweight, rowmeta, y, M, N, K, workspace, ws_bytes, S, stream);
         case MXQ_LAYOUT_MIXEDC: return launch8_slices<MXQ_LAYOUT_MIXEDC>(x, qweight, rowmeta, y, M, N, K, workspace, ws_bytes, S, stream);
     }
-    return -1;
+    return MXQ_E_SHAPE;
 }
-
-size_t G8_SYM(, _workspace_bytes)() { return MXQ_WS_HEAD_BYTES + (size_t)(cu_count() / 8 * 8) * 2 * BM * BN * sizeof(float); }
 
 int G8_SYM(launch_, _f16)(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
                          void* workspace, size_t ws_bytes, int force, hipStream_t stream) {
@@ -1802,7 +1770,7 @@ int G8_SYM(launch_, _layout_f16)(const void* x, const void* qweight, const void*
         case MXQ_LAYOUT_W4ROW: return launch8<0, MXQ_LAYOUT_W4ROW>(x, qweight, rowmeta, y, M, N, K, workspace, ws_bytes, false, stream);
         case MXQ_LAYOUT_MIXEDC: return launch8<0, MXQ_LAYOUT_MIXEDC>(x, qweight, rowmeta, y, M, N, K, workspace, ws_bytes, false, stream);
     }
-    return -1;
+    return MXQ_E_SHAPE;
 }
 
 #if MXQ_G8_BM == 256   // (the dense mode's four DMA waves belong to the 256-token build)
@@ -1845,7 +1813,7 @@ extern "C" int G8_SYM(prof_, _ablate_f16)(const void* x, const void* qweight, co
         case 132: return launch8<132>(x, qweight, rowmeta, y, M, N, K, nullptr, 0, false, stream);
         case 196: return launch8<196>(x, qweight, rowmeta, y, M, N, K, nullptr, 0, false, stream);
     }
-    return -1;   // MXQ_E_SHAPE: not an ablation this build carries
+    return MXQ_E_SHAPE;   // not an ablation this build carries
 }
 
 #if MXQ_G8_BM == 256
@@ -1865,7 +1833,7 @@ __global__ void mxq_prof_occupy_kernel(unsigned long long ticks, int* sink) {
     if (acc == 0x7fffffff) *sink = acc;
 }
 extern "C" int mxq_prof_occupy(int grid, int lds_bytes, unsigned long long usec, void* sink, void* stream_) {
-    if (grid <= 0 || lds_bytes < 256 || lds_bytes > 160 * 1024 || usec > 50000) return -1;       // bounded: never a hang
+    if (grid <= 0 || lds_bytes < 256 || lds_bytes > 160 * 1024 || usec > 50000) return MXQ_E_SHAPE;       // bounded: never a hang
     hipError_t e = hipFuncSetAttribute((const void*)mxq_prof_occupy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     if (e != hipSuccess) return (int)e;
     mxq_prof_occupy_kernel<<<grid, 64, lds_bytes, (hipStream_t)stream_>>>(usec * 100ull, (int*)sink);
@@ -1882,8 +1850,7 @@ extern "C" int G8_SYM(prof_, _dense_f16)(const void* x, const void* w16, void* y
 template <int ABL>
 static int launch8_stamps(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
                           void* dbg, hipStream_t stream) {
-    hipError_t e = hipFuncSetAttribute((const void*)G8_KERNEL<ABL, MXQ_LAYOUT_MIXED>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
+    hipError_t e = mxq_set_dyn_lds_once<&G8_KERNEL<ABL, MXQ_LAYOUT_MIXED>>(SMEM_BYTES);
     if (e != hipSuccess) return (int)e;
     const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
     G8_KERNEL<ABL, MXQ_LAYOUT_MIXED><<<tiles_m * tiles_n, THREADS, SMEM_BYTES, stream>>>(
@@ -1901,7 +1868,7 @@ extern "C" int G8_SYM(prof_, _stamps_f16)(const void* x, const void* qweight, co
         case 4: return launch8_stamps<4096 + 4>(x, qweight, rowmeta, y, M, N, K, dbg, stream);
         case 2: return launch8_stamps<4096 + 2>(x, qweight, rowmeta, y, M, N, K, dbg, stream);
     }
-    return -1;
+    return MXQ_E_SHAPE;
 }
 // fault injection for the expiry test (EXP_SK_WITHHOLD above): the tail always split, unit 0's counts withheld
 extern "C" int G8_SYM(prof_, _skwithhold_f16)(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N,

@@ -31,14 +31,13 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/mxq_hip.h"
+#include "mxq_amdgcn.h"
 #include "mxq_dequant.h"
 #include "mxq_kernels.h"
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef short short4v __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define LDS_AS __attribute__((address_space(3)))
 
 constexpr int DX_BM = 128;          // tokens per tile
@@ -48,7 +47,6 @@ constexpr int DX_THREADS = 512;
 constexpr int DX_W_BYTES = DX_BN * DX_BK * 2;        // 32768
 constexpr int DX_Y_STRIDE = 144;                      // bytes per dy tile row: 128 + 16 of padding
 constexpr int DX_Y_BYTES = DX_BM * DX_Y_STRIDE;      // 18432
-constexpr int DX_CUS = 256;                          // compute units of an MI355X
 
 __device__ __forceinline__ int w_swz(int r) { return 2 * ((r & 3) | ((r >> 1) & 4)); }
 
@@ -243,8 +241,9 @@ int mxq_gemm_dx_slices(int M, int N, int K, size_t slab_bytes) {
     const int steps = (N + DX_BN - 1) / DX_BN;
     const size_t per_slice = (size_t)M * K * 4;
     // fill the chip: one workgroup per CU, at least 4 reduction steps (256 rows of W') per slice, at most 16 slices
-    if (tiles >= DX_CUS) return 1;
-    int S = (DX_CUS + tiles - 1) / tiles;
+    const int cus = mxq_cu_count();
+    if (tiles >= cus) return 1;
+    int S = (cus + tiles - 1) / tiles;
     S = min(S, min(steps / 4, 16));
     S = (int)min((size_t)S, slab_bytes / per_slice);
     return S < 2 ? 1 : S;

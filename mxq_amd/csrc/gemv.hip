@@ -40,6 +40,8 @@
 // bytes) per tile, straight to VGPRs; waves split the tile list.
 #include <hip/hip_runtime.h>
 
+#include "../../include/mxq_hip.h"
+#include "mxq_amdgcn.h"
 #include "mxq_dequant.h"
 #include "mxq_format.h"
 #include "mxq_gemv_common.h"
@@ -143,8 +145,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void mxq_gemv_f16_kernel(const uint16
         uint32_t c2w[NG2 ? NG2 : 1], z2w[NG2 ? NG2 : 1], c4w[NW4 ? NW4 : 1], scw;
         uint2 qq[NG2 ? NG2 : 1];
     };
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(qweight + (int64_t)rb0 * NC * BLK_DW), 0, EPI ? (PS + 1) * NC * BLK_DW * 4 : nrb * NC * BLK_DW * 4, 0x00020000);
+    const rsrc_t rs = make_rsrc(qweight + (int64_t)rb0 * NC * BLK_DW, EPI ? (PS + 1) * NC * BLK_DW * 4 : nrb * NC * BLK_DW * 4);
     const int lane_off = (cs * BLK_DW) * 4;             // byte offset of the lane's block inside a tile
     auto load_tile = [&](int c4) {                      // tile index in the list; beyond its end (or a chunk >= NC): zeros, no traffic
         Tile t = {};
@@ -495,7 +496,7 @@ int mxq_launch_gemv_swiglu_f16(const void* x, const void* qweight, const void* r
                                const void* norm_w, float eps, int compact, hipStream_t stream) {
     const int M = 1;
     const void* residual = nullptr;
-    if (N2 % 32 != 0 || K % 256 != 0) return -1;
+    if (N2 % 32 != 0 || K % 256 != 0) return MXQ_E_SHAPE;
     return compact ? launch_t<1, 256, 1, MXQ_LAYOUT_MIXEDC, 2, 1>(x, qweight, rowmeta, act, M, N2, K, norm_w, eps, residual, stream, act_sum)
                    : launch_t<1, 256, 1, MXQ_LAYOUT_MIXED, 2, 1>(x, qweight, rowmeta, act, M, N2, K, norm_w, eps, residual, stream, act_sum);
 }
@@ -537,7 +538,7 @@ extern "C" int mxq_prof_gemv_fused_f16(const void* x, const void* qweight, const
 // A/B entry for tools/ (correct results): explicit workgroup size (128 / 256 / 512 threads), M = 1
 extern "C" int mxq_prof_gemv_f16(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
                                  int threads, void* stream) {
-    if (M != 1) return -1;
+    if (M != 1) return MXQ_E_SHAPE;
     return launch<1>(x, qweight, rowmeta, y, M, N, K, (hipStream_t)stream, threads);
 }
 #endif

@@ -15,6 +15,7 @@
 // fp32 dequant + fp32 accumulate exactly as the reference does; fp16 output.
 #include <hip/hip_runtime.h>
 
+#include "mxq_amdgcn.h"
 #include "mxq_kernels.h"
 
 namespace {
@@ -24,8 +25,6 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
-
-__device__ __forceinline__ float h2f(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
 
 __device__ __forceinline__ void unpack8h(const uint4 a, float f[8]) {
     const uint32_t w[4] = {a.x, a.y, a.z, a.w};

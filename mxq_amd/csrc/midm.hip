@@ -36,17 +36,12 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/mxq_hip.h"
+#include "mxq_amdgcn.h"
 #include "mxq_dequant.h"
 #include "mxq_format.h"
 #include "mxq_kernels.h"
 
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
 
 constexpr int BN = 128, THREADS = 512, WAVES = 8;
 constexpr int LDS_MAX = 160 * 1024;
@@ -76,16 +71,6 @@ struct Geo {
     static constexpr int SLAB = BM * BN;               // floats per partial tile
     static_assert(DP >= 2 && SMEM <= LDS_MAX, "LDS budget");
 };
-
-__device__ __forceinline__ int swz(int row, int slot) { return row * 128 + ((slot ^ (row & 7)) << 4); }
-__device__ __forceinline__ rsrc_t make_rsrc(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, 0x00020000);
-}
-// LDS-DMA, 16 B per lane: LDS destination = wave-uniform base + 16 * lane; source = descriptor base + voff + soff,
-// out-of-range sources deliver zeros
-__device__ __forceinline__ void dma16(rsrc_t rsrc, uint32_t voff, uint32_t soff, void* l) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)l, 16, voff, soff, 0, 0);
-}
 
 // One thread's task: (row, column half H) of one chunk = 32 weights.  H = 0: 2-bit groups 0, 1; H = 1: group 2 and the
 // two 4-bit code words.  blk: the row block's packed block in the raw ring (mxq_format.h field offsets).
@@ -188,7 +173,7 @@ __device__ __forceinline__ void midm_run(char* smem, const uint16_t* __restrict_
             // a chunk beyond the slice's end: an EMPTY descriptor (every address out of range: zeros land, no traffic)
             const int chunk = c0 + 2 * t + i / G::XPC;
             if (!(MIDM_ABL & 8))
-            dma16(make_rsrc(x + (int64_t)m0 * K, chunk < c1 ? xbytes : 0u), xvoff[i], (uint32_t)chunk * 128u, b + xlds[i]);
+            bufdma16(make_rsrc(x + (int64_t)m0 * K, chunk < c1 ? xbytes : 0u), xvoff[i], (uint32_t)chunk * 128u, b + xlds[i]);
         }
     };
 
@@ -202,8 +187,8 @@ __device__ __forceinline__ void midm_run(char* smem, const uint16_t* __restrict_
         char* b = smem + G::OFF_R + (t % DP) * G::RS_BYTES + wave * BLK_B;
         const rsrc_t wr = make_rsrc(qweight, t < nd ? wbytes : 0u);      // past the slice: empty descriptor, as for x
         if (lane < BLK_B / 16 && !(MIDM_ABL & 16)) {     // 36 lanes (exact metadata) / 30 (compact)
-            dma16(wr, pvoff, (uint32_t)(c0 + 2 * t) * BLK_B, b);
-            dma16(wr, pvoff, (uint32_t)(c0 + 2 * t + 1) * BLK_B, b + 8 * BLK_B);
+            bufdma16(wr, pvoff, (uint32_t)(c0 + 2 * t) * BLK_B, b);
+            bufdma16(wr, pvoff, (uint32_t)(c0 + 2 * t + 1) * BLK_B, b + 8 * BLK_B);
         }
     };
     constexpr int NPI = 2;                                // DMA instructions of one load_p
@@ -446,19 +431,6 @@ __global__ __launch_bounds__(256) void mxq_midm_combine_kernel(const float* __re
     if (m < M && n < N) *(u32x4*)(y + (int64_t)m * N + n) = (u32x4){a[0], a[1], b[0], b[1]};
 }
 
-int cu_count_() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-            cus = n;
-        else
-            cus = 256;
-    }
-    return cus;
-}
-
 template <int BM, bool COMPACT>
 int launch_t(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K, void* workspace,
              size_t ws_bytes, int splits, hipStream_t stream) {
@@ -468,7 +440,7 @@ int launch_t(const void* x, const void* qweight, const void* rowmeta, void* y, i
     // slices: as many as keep tiles x S within one workgroup per CU, at least 2 double-steps (4 chunks) each
     int S = 1;
     if (workspace && ws_bytes > MXQ_WS_HEAD_BYTES) {
-        S = splits > 0 ? splits : cu_count_() / tiles;
+        S = splits > 0 ? splits : mxq_cu_count() / tiles;
         if (S > NC / 4) S = NC / 4;
         const size_t room = (ws_bytes - MXQ_WS_HEAD_BYTES) / ((size_t)tiles * G::SLAB * sizeof(float));
         if ((size_t)S > room) S = (int)room;
@@ -518,9 +490,9 @@ bool mxq_midm_fits(int N, int K) {
 // the CU count, else the number of K slices asked for (clamped to what K and the workspace allow).
 int mxq_launch_midm_f16(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K, int layout,
                         void* workspace, size_t ws_bytes, int bm, int splits, hipStream_t stream) {
-    if (layout != MXQ_LAYOUT_MIXED && layout != MXQ_LAYOUT_MIXEDC) return -1;
-    if (bm != 0 && bm != 64 && bm != 128) return -1;
-    if (!mxq_midm_fits(N, K)) return -1;
+    if (layout != MXQ_LAYOUT_MIXED && layout != MXQ_LAYOUT_MIXEDC) return MXQ_E_SHAPE;
+    if (bm != 0 && bm != 64 && bm != 128) return MXQ_E_SHAPE;
+    if (!mxq_midm_fits(N, K)) return MXQ_E_SHAPE;
     if (bm == 0) bm = M <= 64 ? 64 : 128;
     const bool c = layout == MXQ_LAYOUT_MIXEDC;
     if (bm == 64)

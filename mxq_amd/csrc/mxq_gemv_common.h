@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mxq_amdgcn.h"   // and_or
+
 namespace {
 
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
@@ -11,14 +13,6 @@ typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ float dot2(uint32_t w, uint32_t x, float acc) {
     return __builtin_amdgcn_fdot2(__builtin_bit_cast(half2v, w), __builtin_bit_cast(half2v, x), acc, false);
-}
-
-// (a & m) | o in one op (the mask in an SGPR, the fp16 ones in a VGPR: gfx9 VOP3 takes no literals, and left to itself
-// the compiler emits v_and + v_or)
-__device__ __forceinline__ uint32_t and_or(uint32_t a, uint32_t m, uint32_t o) {
-    uint32_t r;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(m), "v"(o));
-    return r;
 }
 
 // sum_k (1 + q_k / 4) x_k over the 16 two-bit codes of byte-spread word d.  Element k sits at bit 8 (k & 3) +

@@ -103,6 +103,26 @@ inline int mxq_resident_workgroups(int threads, size_t smem) {
     if (slot) cached[dev].store(total, std::memory_order_relaxed);
     return total > 0 ? total : 0;
 }
+
+// The current device's compute-unit count, asked once per device ordinal and cached.  256 (an MI355X) when the query fails
+// or answers fewer than 8: the count that sizes the workspaces on a machine without a GPU.  Callers that deal work to whole
+// XCDs (8 CUs each) round it down themselves.
+inline int mxq_cu_count() {
+    static std::atomic<int> cached[64];
+    int dev = 0;
+    const bool slot = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64;
+    if (slot) {
+        const int c = cached[dev].load(std::memory_order_relaxed);
+        if (c != 0) return c;
+    }
+    int n = 0;
+    if (!slot || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) {
+        (void)hipGetLastError();
+        n = 256;
+    }
+    if (slot) cached[dev].store(n, std::memory_order_relaxed);
+    return n;
+}
 #endif
 // the same product with a 256 x 256 tile and a quadrant-phase ping-pong schedule (dense256.hip); MXQ_NOT_MY_SHAPE: odd
 // K-tile count, or -- unless force -- too few tiles to fill the chip twice: take the kernel above

@@ -22,15 +22,14 @@
 // slice with the row's scale / zero-point) -- the reference serves uniform W4 at any batch (gemv_cuda.cu:346-399).
 #include <hip/hip_runtime.h>
 
+#include "mxq_amdgcn.h"
+#include "../../include/mxq_hip.h"
+#include "mxq_amdgcn.h"
 #include "mxq_dequant.h"
 #include "mxq_format.h"
 #include "mxq_kernels.h"
 
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // half `h` (8 weights) of a 2-bit group -> 4 packed fp16 pairs
 MXQ_HD void deq2_half(uint32_t d, int h, float s, float z, uint32_t o[4]) {
@@ -205,12 +204,12 @@ int launch_c(const void* x, const void* qweight, const void* rowmeta, void* y, i
 // 1 <= M <= 64; any layout
 int mxq_launch_skinny_f16(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
                           int layout, hipStream_t stream) {
-    if (M < 1 || M > 64) return -1;
+    if (M < 1 || M > 64) return MXQ_E_SHAPE;
     switch (layout) {
         case MXQ_LAYOUT_MIXED: return launch_c<MXQ_LAYOUT_MIXED>(x, qweight, rowmeta, y, M, N, K, stream);
         case MXQ_LAYOUT_MIXEDC: return launch_c<MXQ_LAYOUT_MIXEDC>(x, qweight, rowmeta, y, M, N, K, stream);
         case MXQ_LAYOUT_W2G16: return launch_c<MXQ_LAYOUT_W2G16>(x, qweight, rowmeta, y, M, N, K, stream);
         case MXQ_LAYOUT_W4ROW: return launch_c<MXQ_LAYOUT_W4ROW>(x, qweight, rowmeta, y, M, N, K, stream);
     }
-    return -1;
+    return MXQ_E_SHAPE;
 }

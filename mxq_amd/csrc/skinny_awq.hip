@@ -23,30 +23,17 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/mxq_hip.h"
+#include "mxq_amdgcn.h"
 #include "mxq_kernels.h"
 
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
 
 constexpr int BN = 128, NB = BN / 16;
 // one counter per channel block at the workspace's head (shared with the stream-K kernels: zero when idle), at most this many bytes
 constexpr int CNT_MAX_BYTES = 16384;
 static_assert(CNT_MAX_BYTES <= MXQ_WS_MAILBOX_OFFSET, "counters end below the mailbox");
-
-__device__ __forceinline__ rsrc_t make_rsrc(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, 0x00020000);
-}
-__device__ __forceinline__ uint32_t and_or(uint32_t a, uint32_t m, uint32_t o) {   // (a & m) | o: mask in an SGPR, constant in a VGPR
-    uint32_t r;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(m), "v"(o));
-    return r;
-}
 
 // byte of a code word that holds channel e of its octet, and whether it is the byte's high nibble: channel e sits in nibble
 // (0, 4, 1, 5, 2, 6, 3, 7)[e] (dequantize.cuh:35-51)
@@ -90,8 +77,7 @@ __global__ __launch_bounds__(WAVES * 64) void mxq_skinny_awq_f16_kernel(const ui
             const uint32_t so = (uint32_t)(k0 + g * 32) * row_bytes;
 #pragma unroll
             for (int j = 0; j < 2; ++j)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_q, (__attribute__((address_space(3))) void*)(smem + g * 2048 + j * 1024), 16,
-                                                         voff[j], so, 0, 0);
+                bufdma16(rs_q, voff[j], so, smem + g * 2048 + j * 1024);
         }
     }
 
@@ -259,9 +245,7 @@ int launch_nj(const void* x, const void* kernel, const void* scales, const void*
               void* workspace, size_t ws_bytes, hipStream_t stream) {
     constexpr int WAVES = NJ <= 2 ? 8 : 4, THREADS = WAVES * 64;
     const int nblk = (OC + BN - 1) / BN, NT = IC / 64;
-    int cus = 256, dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        cus = 256;
+    const int cus = mxq_cu_count();
     // K slices: one workgroup per CU (blocks x S <= CUs) -- or two, where that leaves a quarter of the chip idle (86 blocks: 2 slices
     // = 172 workgroups) and a slice's code words (64 B per row) and the reduction scratch (32 KiB per token block), which share
     // the LDS, leave room for two workgroups on a CU
@@ -306,8 +290,8 @@ int mxq_launch_skinny_awq_f16(const void* x, const void* kernel, const void* sca
                               int G, void* workspace, size_t ws_bytes, hipStream_t stream) {
     if (M > 32) return MXQ_NOT_MY_SHAPE;
     if (M < 1 || IC < 64 || IC % 64 != 0 || OC % 8 != 0 || OC < 32 || G < 32 || G % 32 != 0 || IC % G != 0 || G >= 4096 || IC >= (1 << 20))
-        return -1;
-    if ((int64_t)IC * OC / 2 >= ((int64_t)1 << 31) || (int64_t)(IC / G) * OC * 2 >= ((int64_t)1 << 31)) return -1;
+        return MXQ_E_SHAPE;
+    if ((int64_t)IC * OC / 2 >= ((int64_t)1 << 31) || (int64_t)(IC / G) * OC * 2 >= ((int64_t)1 << 31)) return MXQ_E_SHAPE;
     if (M <= 16) return launch_nj<1>(x, kernel, scales, zeros, y, M, IC, OC, G, workspace, ws_bytes, stream);
     return launch_nj<2>(x, kernel, scales, zeros, y, M, IC, OC, G, workspace, ws_bytes, stream);
 }
