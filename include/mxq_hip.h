@@ -396,9 +396,29 @@ int mxq_gemv_awq_f16(const void* x, const void* kernel, const void* scales, cons
  * arriver of a channel block sums the slices; csrc/skinny_awq.hip), then 64- / 128-token tiles by tile count (K slices + a combine
  * launch, or stream-K), beyond that 256-token tiles with a stream-K tail -- through `workspace` (mxq_gemm_workspace_bytes() bytes, 16-byte
  * aligned, counter head zeroed as for mxq_linear_f16_ws; NULL: whole tiles only).  Deterministic.  MXQ_E_SHAPE for the
- * launcher's rejections (OC % 64, group_size % 32, OC % group_size) and for IC % 64, IC % group_size. */
+ * launcher's rejections (OC % 64, group_size % 32, OC % group_size), for IC % 64, IC % group_size, for IC * group_size > 2^32
+ * (the group index is a multiply-high by a reciprocal, exact up to there: one group per output channel, group_size = IC, is
+ * fine) and for a non-NULL workspace of fewer than MXQ_WS_HEAD_BYTES.  x, kernel, scales, y and the workspace 16-byte aligned
+ * (the code words are fetched with 16-byte loads), zeros 4-byte aligned, else MXQ_E_ALIGN. */
 int mxq_gemm_awq_f16(const void* x, const void* kernel, const void* scales, const void* zeros, void* y, int M, int IC, int OC,
                      int group_size, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The schedule mxq_gemm_awq_f16 runs for a call of this shape with `workspace_bytes` of workspace (0: NULL), from the same
+ * host function the entry dispatches on -- no device work; MXQ_E_SHAPE where the entry rejects the shape.
+ * mxq_gemm_awq_workspace_need: the bytes of workspace that schedule uses when given mxq_gemm_workspace_bytes() (0: none);
+ * with that many the entry runs the same schedule, bit for bit the same result. */
+enum mxq_awq_sched {
+    MXQ_AWQ_SKINNY = 1,             /* streaming kernel (csrc/skinny_awq.hip), one K slice per channel block */
+    MXQ_AWQ_SKINNY_SLICED = 2,      /* ... K slices, summed by the last arriver through the workspace */
+    MXQ_AWQ_FUSED64_SLICES = 3,     /* the fused kernel's 64-token build (csrc/gemm8aq.hip): K slices + combine launch */
+    MXQ_AWQ_FUSED64_STREAMK = 4,    /* ... stream-K */
+    MXQ_AWQ_FUSED64 = 5,            /* ... whole tiles, no workspace */
+    MXQ_AWQ_FUSED128_SLICES = 6,    /* its 128-token build (csrc/gemm8ah.hip) */
+    MXQ_AWQ_FUSED128_STREAMK = 7,
+    MXQ_AWQ_FUSED256 = 8            /* its 256-token build (csrc/gemm8a.hip): whole tiles, a stream-K tail where it pays */
+};
+int mxq_gemm_awq_schedule(int M, int IC, int OC, int group_size, size_t workspace_bytes);
+size_t mxq_gemm_awq_workspace_need(int M, int IC, int OC, int group_size);
 
 /* gemv_mxq_forward_cuda(in_feats, kernel, kernel_last, zeros_and_scales, scales_2nd,
  * zeros_2nd, scales_4b, zeros_4b, group_size) (gemv_mxq_cuda.h:4-12; operand layout

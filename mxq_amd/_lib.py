@@ -21,6 +21,9 @@ WS_HEAD_BYTES, WS_MAILBOX_OFFSET, WS_STATUS_OFFSET = 65536, 65504, 65520
 SCHED_NAMES = {1: "gemv", 2: "skinny", 3: "midm", 4: "fused64_streamk", 5: "fused64_slices", 6: "fused128_streamk",
                7: "fused128_slices", 8: "fused128n64_streamk", 9: "fused128n64_slices", 10: "fused256", 11: "tile128",
                12: "hoisted"}
+# mxq_gemm_awq_schedule's result: include/mxq_hip.h enum mxq_awq_sched
+AWQ_SCHED_NAMES = {1: "skinny", 2: "skinny_sliced", 3: "fused64_slices", 4: "fused64_streamk", 5: "fused64", 6: "fused128_slices",
+                   7: "fused128_streamk", 8: "fused256"}
 
 _ERRORS = {-1: "invalid shape (need N % 16 == 0, K % 64 == 0, positive sizes, supported group size)",
            -2: "null pointer", -3: "unknown dtype code", -4: "pointer not 16-byte aligned"}
@@ -90,6 +93,8 @@ SIGNATURES = {
     "mxq_fakequant_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_int, c_void_p]),
     "mxq_gemv_awq_f16": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_void_p]),
     "mxq_gemm_awq_f16": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "mxq_gemm_awq_schedule": (c_int, [c_int, c_int, c_int, c_int, c_size_t]),
+    "mxq_gemm_awq_workspace_need": (c_size_t, [c_int, c_int, c_int, c_int]),
     "mxq_gemv_proto_f16": (c_int, [c_void_p] * 9 + [c_int, c_int, c_int, c_int, c_void_p]),
 }
 

@@ -632,36 +632,81 @@ int mxq_gemv_awq_f16(const void* x, const void* kernel, const void* scales, cons
     return mxq_launch_gemv_awq_f16(x, kernel, scales, zeros, y, B, IC, OC, group_size, (hipStream_t)stream);
 }
 
+// ---- gemm_forward_cuda's operand format: ONE dispatch rule (include/mxq_hip.h, enum mxq_awq_sched) ---------------------------
+// Up to 32 tokens: a streaming kernel (one workgroup per 128 channels x K slice, last arriver sums the slices), unless the K range
+// does not fit its LDS (mxq_skinny_awq_slices).  Beyond -- and as its fallback -- the fused kernel's dispatch by tile count
+// (plan_linear above) on this operand format's builds: 64-token tiles, then 128-token tiles while there are at most 176 of them
+// (<= 1024 tokens) -- <= 64 tiles: every tile's K range cut so that tiles x slices fill the chip, partial tiles summed by a combine
+// launch; 65 .. 176 tiles: one launch, stream-K over the otherwise idle CUs (both need the workspace) -- beyond that 256-token
+// tiles, persistent, stream-K tail.  Host-only, like plan_linear; ws_bytes 0: no workspace.
+namespace {
+bool awq_shape_ok(int M, int IC, int OC, int G) {
+    // the reference launcher's checks (gemm_cuda_gen.cu:447-454) + this kernel's 64-deep K-step + an exact group index
+    if (M <= 0 || IC <= 0 || OC <= 0 || OC % 64 != 0 || OC % 8 != 0) return false;
+    if (G <= 0 || G % 32 != 0 || OC % G != 0) return false;
+    return IC % 64 == 0 && IC % G == 0 && mxq_awq_gmul_exact(IC, G);
+}
+LinearPlan plan_awq(int M, int IC, int OC, size_t ws_bytes) {
+    const int tn = (OC + 127) / 128;
+    if (M <= 32) {
+        size_t need;
+        const int S = mxq_skinny_awq_slices(M, IC, OC, ws_bytes, &need);
+        if (S == 1) return {MXQ_AWQ_SKINNY, 0};
+        if (S > 1) return {MXQ_AWQ_SKINNY_SLICED, need};
+    }
+    if (M <= 64) {
+        const size_t need = mxq_gemm8aq_workspace_bytes();
+        if (ws_bytes >= need && tn <= STREAMK_MAX_TILES)
+            return {tn <= SLICES_MAX_TILES ? MXQ_AWQ_FUSED64_SLICES : MXQ_AWQ_FUSED64_STREAMK, need};
+        if (!ws_bytes) return {MXQ_AWQ_FUSED64, 0};
+    }
+    const int t128 = ((M + 127) / 128) * tn;
+    if (const size_t need = mxq_gemm8ah_workspace_bytes(); M <= 1024 && ws_bytes >= need && t128 <= STREAMK_MAX_TILES)
+        return {t128 <= SLICES_MAX_TILES ? MXQ_AWQ_FUSED128_SLICES : MXQ_AWQ_FUSED128_STREAMK, need};
+    return {MXQ_AWQ_FUSED256, mxq_gemm8a_workspace_bytes()};
+}
+}   // namespace
+
 int mxq_gemm_awq_f16(const void* x, const void* kernel, const void* scales, const void* zeros, void* y, int M, int IC, int OC,
                      int group_size, void* workspace, size_t workspace_bytes, void* stream) {
     if (!x || !kernel || !scales || !zeros || !y) return MXQ_E_NULL;
-    // the reference launcher's checks (gemm_cuda_gen.cu:447-454) + this kernel's 64-deep K-step
-    if (M <= 0 || IC <= 0 || OC <= 0 || OC % 64 != 0 || OC % 8 != 0) return MXQ_E_SHAPE;
-    if (group_size <= 0 || group_size % 32 != 0 || OC % group_size != 0) return MXQ_E_SHAPE;
-    if (IC % 64 != 0 || IC % group_size != 0) return MXQ_E_SHAPE;
-    if (!aligned16(x) || !aligned16(scales) || !aligned16(y) || ((uintptr_t)kernel & 3) || ((uintptr_t)zeros & 3)) return MXQ_E_ALIGN;
+    if (!awq_shape_ok(M, IC, OC, group_size)) return MXQ_E_SHAPE;
+    // the code words go through 16-byte LDS-DMA (bufdma16): kernel 16-byte aligned; zeros are read a dword at a time
+    if (!aligned16(x) || !aligned16(kernel) || !aligned16(scales) || !aligned16(y) || ((uintptr_t)zeros & 3)) return MXQ_E_ALIGN;
     if (workspace && !aligned16(workspace)) return MXQ_E_ALIGN;
     if (workspace && workspace_bytes < MXQ_WS_HEAD_BYTES) return MXQ_E_SHAPE;
-    // Up to 32 tokens: a streaming kernel (one workgroup per 128 channels x K slice, last arriver sums the slices).  Beyond -- and as
-    // its fallback -- the fused kernel's dispatch by tile count (plan_linear above) on this operand format's builds:
-    // 64-token tiles, then 128-token tiles while there are at most 176 of them (<= 1024 tokens) -- <= 64 tiles: every tile's K range cut so that tiles x slices fill the
-    // chip, partial tiles summed by a combine launch; 65 .. 176 tiles: one launch, stream-K over the otherwise idle CUs (both need
-    // the workspace) -- beyond that 256-token tiles, persistent, stream-K tail.
+    if (!workspace) workspace_bytes = 0;
     hipStream_t st = (hipStream_t)stream;
-    const int tn = (OC + 127) / 128;
-    if (M <= 32) {     // few tokens: the streaming kernel (skinny_awq.hip), unless the K range does not fit its LDS unsliced
-        const int e = mxq_launch_skinny_awq_f16(x, kernel, scales, zeros, y, M, IC, OC, group_size, workspace, workspace_bytes, st);
-        if (e != MXQ_NOT_MY_SHAPE) return e;
+    void* ws = workspace;
+    switch (plan_awq(M, IC, OC, workspace_bytes).sched) {
+        case MXQ_AWQ_SKINNY:
+        case MXQ_AWQ_SKINNY_SLICED:
+            return mxq_launch_skinny_awq_f16(x, kernel, scales, zeros, y, M, IC, OC, group_size, ws, workspace_bytes, st);
+        case MXQ_AWQ_FUSED64_SLICES:
+        case MXQ_AWQ_FUSED64_STREAMK:
+        case MXQ_AWQ_FUSED64: {
+            const int tn = (OC + 127) / 128;
+            return mxq_launch_gemm8aq_f16(x, kernel, scales, zeros, y, M, IC, OC, group_size, ws, workspace_bytes,
+                                          !ws ? 0 : tn <= SLICES_MAX_TILES ? -1 : -2, st);
+        }
+        case MXQ_AWQ_FUSED128_SLICES:
+        case MXQ_AWQ_FUSED128_STREAMK: {
+            const int t128 = ((M + 127) / 128) * ((OC + 127) / 128);
+            return mxq_launch_gemm8ah_f16(x, kernel, scales, zeros, y, M, IC, OC, group_size, ws, workspace_bytes,
+                                          t128 <= SLICES_MAX_TILES ? -1 : -2, st);
+        }
     }
-    if (M <= 64 && workspace && workspace_bytes >= mxq_gemm8aq_workspace_bytes() && tn <= STREAMK_MAX_TILES)
-        return mxq_launch_gemm8aq_f16(x, kernel, scales, zeros, y, M, IC, OC, group_size, workspace, workspace_bytes,
-                                      tn <= SLICES_MAX_TILES ? -1 : -2, st);
-    if (M <= 64 && !workspace) return mxq_launch_gemm8aq_f16(x, kernel, scales, zeros, y, M, IC, OC, group_size, nullptr, 0, 0, st);
-    const int t128 = ((M + 127) / 128) * tn;
-    if (M <= 1024 && workspace && workspace_bytes >= mxq_gemm8ah_workspace_bytes() && t128 <= STREAMK_MAX_TILES)
-        return mxq_launch_gemm8ah_f16(x, kernel, scales, zeros, y, M, IC, OC, group_size, workspace, workspace_bytes,
-                                      t128 <= SLICES_MAX_TILES ? -1 : -2, st);
-    return mxq_launch_gemm8a_f16(x, kernel, scales, zeros, y, M, IC, OC, group_size, workspace, workspace_bytes, 0, st);
+    return mxq_launch_gemm8a_f16(x, kernel, scales, zeros, y, M, IC, OC, group_size, ws, workspace_bytes, 0, st);
+}
+
+int mxq_gemm_awq_schedule(int M, int IC, int OC, int group_size, size_t workspace_bytes) {
+    if (!awq_shape_ok(M, IC, OC, group_size)) return MXQ_E_SHAPE;
+    return plan_awq(M, IC, OC, workspace_bytes).sched;
+}
+
+size_t mxq_gemm_awq_workspace_need(int M, int IC, int OC, int group_size) {
+    if (!awq_shape_ok(M, IC, OC, group_size)) return 0;
+    return plan_awq(M, IC, OC, mxq_gemm_workspace_bytes()).ws_need;
 }
 
 int mxq_gemv_proto_f16(const void* x, const void* weight, const void* weight_last, const void* zeros_and_scales,

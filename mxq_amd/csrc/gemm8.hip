@@ -138,7 +138,7 @@ static_assert(MXQ_G8_BN == 128, "the AWQ dequant waves cover 16 channel octets")
 struct AwqOps {
     const uint16_t* scales;   // fp16 [K / G, N]
     const uint32_t* zeros;    // int32 [K / G, N / 8], nibble order of the code words
-    uint32_t gmul;            // floor(2^32 / G) + 1: k / G = mulhi(k, gmul) for every k < 2^20 (G < 2^12)
+    uint32_t gmul;            // mxq_awq_gmul(G): k / G = mulhi(k, gmul) for every k < K (launcher: mxq_awq_gmul_exact)
     int groups;               // K / G
 };
 #define G8_AWQ_PARAM , AwqOps awq
@@ -1258,8 +1258,14 @@ __device__ __forceinline__ void awq_segment_raw1(Deq& c, const Deq& nxt, bool pr
         issue_zs(0, nx);
         issue_dma(0, slot);
         issue_dma(1, slot == 2 ? 0 : slot + 1);
+    } else if (NT == 1) {
+        // the previous segment fetched "chunk 1" as the words of THIS segment's second K-step, which a one-step segment does
+        // not have (IC = 64, or a one-step stream-K piece): that slot must hold nxt's chunk 0.  Let the stale DMA land, then
+        // fetch the right words over it (the loop's vmcnt(4) below waits for this one as for any older operation).
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        issue_dma(1, slot == 2 ? 0 : slot + 1);
     }
-    // in flight at most: z/s(0), DMA(0), DMA(1) in this order (pre: z/s(0), DMA(1)) -- chunk 0's words have landed once at most
+    // in flight at most: z/s(0), DMA(0), DMA(1) in this order (pre: z/s(0), DMA(1); or DMA(1) alone) -- chunk 0's words have landed once at most
     // one operation is outstanding
     asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
     __builtin_amdgcn_s_barrier();              // prologue barrier 1
@@ -1707,7 +1713,7 @@ static int launch8_slices(const void* x, const void* qweight, const void* rowmet
     const size_t room = workspace && ws_bytes > MXQ_WS_HEAD_BYTES ? (ws_bytes - MXQ_WS_HEAD_BYTES) / ((size_t)tiles * BM * BN * sizeof(float)) : 0;
     if ((size_t)S > room) S = (int)room;
     if (S <= 1) return launch8<0, LAYOUT>(x, qweight, rowmeta, y, M, N, K, nullptr, 0, false, stream G8_AWQ_ARG);
-    if (M <= 0 || N <= 0 || K < BK || K % BK != 0 || N % (LAYOUT == LAYOUT_AWQ ? 8 : 16) != 0) return MXQ_E_SHAPE;
+    if (M <= 0 || N <= 0 || K < BK || K % BK != 0 || N % (LAYOUT == LAYOUT_AWQ ? 32 : 16) != 0) return MXQ_E_SHAPE;
     if (!offsets_fit(N, K)) return MXQ_E_SHAPE;
     hipError_t e = mxq_set_dyn_lds_once<&G8_KERNEL<0, LAYOUT>>(SMEM_BYTES);
     if (e != hipSuccess) return (int)e;
@@ -1731,13 +1737,16 @@ size_t G8_SYM(, _workspace_bytes)() { return MXQ_WS_HEAD_BYTES + (size_t)(mxq_cu
 // tail always split (launches of few tiles).
 int G8_SYM(launch_, _f16)(const void* x, const void* kernel, const void* scales, const void* zeros, void* y, int M, int IC, int OC,
                          int G, void* workspace, size_t ws_bytes, int slices, hipStream_t stream) {
-    if (M <= 0 || IC < BK || IC % BK != 0 || OC <= 0 || OC % 8 != 0 || G < 8 || G % 8 != 0 || IC % G != 0 || G >= 4096 || IC >= (1 << 20))
+    // OC % 32: the code-word DMA clamps a 4-octet quad to the last one (deq_setup), right only for whole quads;
+    // IC * G <= 2^32: k / G = mulhi(k, gmul) exactly for every k < IC (mxq_awq_gmul)
+    if (M <= 0 || IC < BK || IC % BK != 0 || OC < 32 || OC % 32 != 0 || G < 8 || G % 8 != 0 || IC % G != 0 || IC >= (1 << 20) ||
+        !mxq_awq_gmul_exact(IC, G))
         return MXQ_E_SHAPE;
     if ((int64_t)IC * OC / 2 >= ((int64_t)1 << 31) || (int64_t)(IC / G) * OC * 2 >= ((int64_t)1 << 31)) return MXQ_E_SHAPE;
     AwqOps awq;
     awq.scales = (const uint16_t*)scales;
     awq.zeros = (const uint32_t*)zeros;
-    awq.gmul = (uint32_t)(((uint64_t)1 << 32) / (uint32_t)G) + 1u;
+    awq.gmul = mxq_awq_gmul(G);
     awq.groups = IC / G;
     if (slices == -2)    // stream-K, the tail always split
         return launch8<0, LAYOUT_AWQ>(x, kernel, nullptr, y, M, OC, IC, workspace, ws_bytes, true, stream, awq);

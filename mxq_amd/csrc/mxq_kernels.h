@@ -184,8 +184,17 @@ int mxq_launch_gemm8aq_f16(const void* x, const void* kernel, const void* scales
 int mxq_launch_gemm8ah_f16(const void* x, const void* kernel, const void* scales, const void* zeros, void* y, int M, int IC, int OC,
                            int G, void* workspace, size_t ws_bytes, int slices, hipStream_t stream);
 size_t mxq_gemm8ah_workspace_bytes();
+// The AWQ kernels' group index k / G as mulhi(k, gmul), gmul = floor(2^32 / G) + 1 = (2^32 + e) / G with 1 <= e <= G:
+// mulhi(k, gmul) = floor(k / G + k e / (G 2^32)), and the second term moves the floor only if it reaches 1 - frac(k / G) >= 1 / G,
+// i.e. k e >= 2^32.  So the quotient is exact for every k < K whenever K G <= 2^32 (e <= G) -- for any G >= 2, the one-group-per-
+// channel G = K = 4096 included.
+inline uint32_t mxq_awq_gmul(int G) { return (uint32_t)(((uint64_t)1 << 32) / (uint32_t)G) + 1u; }
+inline bool mxq_awq_gmul_exact(int K, int G) { return G >= 2 && K > 0 && (uint64_t)K * (uint64_t)G <= ((uint64_t)1 << 32); }
 // the same operand format for <= 32 tokens: a streaming kernel (skinny_awq.hip); workspace nullable (then one K slice per block);
-// MXQ_NOT_MY_SHAPE: the K range does not fit its LDS unsliced
+// MXQ_NOT_MY_SHAPE: the K range does not fit its LDS unsliced.  mxq_skinny_awq_slices: the K slices it runs with ws_bytes of
+// workspace (0: none) -- 0 where it declines (host only; the launcher and capi.hip's dispatch both ask it); *ws_need: the bytes
+// those slices use (0 for one)
+int mxq_skinny_awq_slices(int M, int IC, int OC, size_t ws_bytes, size_t* ws_need);
 int mxq_launch_skinny_awq_f16(const void* x, const void* kernel, const void* scales, const void* zeros, void* y, int M, int IC, int OC,
                               int G, void* workspace, size_t ws_bytes, hipStream_t stream);
 size_t mxq_gemm8a_workspace_bytes();

@@ -242,10 +242,29 @@ __global__ __launch_bounds__(WAVES * 64) void mxq_skinny_awq_f16_kernel(const ui
 
 template <int NJ>
 int launch_nj(const void* x, const void* kernel, const void* scales, const void* zeros, void* y, int M, int IC, int OC, int G,
-              void* workspace, size_t ws_bytes, hipStream_t stream) {
+              void* workspace, int S, hipStream_t stream) {
     constexpr int WAVES = NJ <= 2 ? 8 : 4, THREADS = WAVES * 64;
     const int nblk = (OC + BN - 1) / BN, NT = IC / 64;
+    const int rows_per_slice = (NT + S - 1) / S * 64;
+    size_t smem = (size_t)rows_per_slice * 64;
+    const size_t red = (size_t)WAVES * NB * NJ * 64 * 16;
+    if (red > smem) smem = red;
+    hipError_t e = mxq_set_dyn_lds_once<&mxq_skinny_awq_f16_kernel<NJ, WAVES>>(160 * 1024 - 64);
+    if (e != hipSuccess) return (int)e;
+    const uint32_t gmul = mxq_awq_gmul(G);
+    mxq_skinny_awq_f16_kernel<NJ, WAVES><<<nblk * S, THREADS, smem, stream>>>(
+        (const uint16_t*)x, (const uint32_t*)kernel, (const uint16_t*)scales, (const uint32_t*)zeros, (uint16_t*)y, M, IC, OC, gmul, IC / G, S,
+        rows_per_slice, (int*)workspace, workspace ? (float*)((char*)workspace + MXQ_WS_HEAD_BYTES) : nullptr);
+    return (int)hipGetLastError();
+}
+
+}   // namespace
+
+int mxq_skinny_awq_slices(int M, int IC, int OC, size_t ws_bytes, size_t* ws_need) {
+    const int NJ = M <= 16 ? 1 : 2, WAVES = 8;                // launch_nj's instantiations
+    const int nblk = (OC + BN - 1) / BN, NT = IC / 64;
     const int cus = mxq_cu_count();
+    *ws_need = 0;
     // K slices: one workgroup per CU (blocks x S <= CUs) -- or two, where that leaves a quarter of the chip idle (86 blocks: 2 slices
     // = 172 workgroups) and a slice's code words (64 B per row) and the reduction scratch (32 KiB per token block), which share
     // the LDS, leave room for two workgroups on a CU
@@ -259,39 +278,32 @@ int launch_nj(const void* x, const void* kernel, const void* scales, const void*
         if (S2 > S && (words2 > red2 ? words2 : red2) <= 78 * 1024) S = S2;
     }
     const size_t slot = (size_t)BN * 16 * NJ * sizeof(float);
-    if (!workspace || nblk * (int)sizeof(int) > CNT_MAX_BYTES) S = 1;
+    if (!ws_bytes || nblk * (int)sizeof(int) > CNT_MAX_BYTES) S = 1;
     while (S > 1 && ws_bytes < (size_t)MXQ_WS_HEAD_BYTES + (size_t)nblk * S * slot) --S;
     int steps = (NT + S - 1) / S;
     while (steps * 64 > 2304) {                              // the slice must fit the LDS: more slices if there is a workspace for them
-        if (!workspace || nblk * (int)sizeof(int) > CNT_MAX_BYTES) return MXQ_NOT_MY_SHAPE;
+        if (!ws_bytes || nblk * (int)sizeof(int) > CNT_MAX_BYTES) return 0;
         ++S;
-        if (ws_bytes < (size_t)MXQ_WS_HEAD_BYTES + (size_t)nblk * S * slot) return MXQ_NOT_MY_SHAPE;
+        if (ws_bytes < (size_t)MXQ_WS_HEAD_BYTES + (size_t)nblk * S * slot) return 0;
         steps = (NT + S - 1) / S;
     }
-    S = (NT + steps - 1) / steps;                            // no empty slice
-    const int rows_per_slice = steps * 64;
-    size_t smem = (size_t)rows_per_slice * 64;
-    const size_t red = (size_t)WAVES * NB * NJ * 64 * 16;
-    if (red > smem) smem = red;
-    hipError_t e = mxq_set_dyn_lds_once<&mxq_skinny_awq_f16_kernel<NJ, WAVES>>(160 * 1024 - 64);
-    if (e != hipSuccess) return (int)e;
-    const uint32_t gmul = (uint32_t)(((uint64_t)1 << 32) / (uint32_t)G) + 1u;
-    mxq_skinny_awq_f16_kernel<NJ, WAVES><<<nblk * S, THREADS, smem, stream>>>(
-        (const uint16_t*)x, (const uint32_t*)kernel, (const uint16_t*)scales, (const uint32_t*)zeros, (uint16_t*)y, M, IC, OC, gmul, IC / G, S,
-        rows_per_slice, (int*)workspace, workspace ? (float*)((char*)workspace + MXQ_WS_HEAD_BYTES) : nullptr);
-    return (int)hipGetLastError();
+    // (with exactly these bytes the loops above stop at the same S: the first cuts it to what fits, and its slices fit the LDS)
+    if (S > 1) *ws_need = (size_t)MXQ_WS_HEAD_BYTES + (size_t)nblk * S * slot;
+    return (NT + steps - 1) / steps;                         // no empty slice
 }
 
-}   // namespace
-
-// 1 <= M <= 32; IC % 64 == 0, OC % 8 == 0, G % 32 == 0 (one quantisation group per 32-row step), IC % G == 0.  MXQ_NOT_MY_SHAPE:
+// 1 <= M <= 32; IC % 64 == 0, OC % 32 == 0, G % 32 == 0 (one quantisation group per 32-row step), IC % G == 0.  MXQ_NOT_MY_SHAPE:
 // more tokens, or a K range that does not fit the LDS without slices and no workspace to slice with (caller: the tile kernel).
 int mxq_launch_skinny_awq_f16(const void* x, const void* kernel, const void* scales, const void* zeros, void* y, int M, int IC, int OC,
                               int G, void* workspace, size_t ws_bytes, hipStream_t stream) {
     if (M > 32) return MXQ_NOT_MY_SHAPE;
-    if (M < 1 || IC < 64 || IC % 64 != 0 || OC % 8 != 0 || OC < 32 || G < 32 || G % 32 != 0 || IC % G != 0 || G >= 4096 || IC >= (1 << 20))
+    if (M < 1 || IC < 64 || IC % 64 != 0 || OC % 32 != 0 || OC < 32 || G < 32 || G % 32 != 0 || IC % G != 0 || IC >= (1 << 20) ||
+        !mxq_awq_gmul_exact(IC, G))
         return MXQ_E_SHAPE;
     if ((int64_t)IC * OC / 2 >= ((int64_t)1 << 31) || (int64_t)(IC / G) * OC * 2 >= ((int64_t)1 << 31)) return MXQ_E_SHAPE;
-    if (M <= 16) return launch_nj<1>(x, kernel, scales, zeros, y, M, IC, OC, G, workspace, ws_bytes, stream);
-    return launch_nj<2>(x, kernel, scales, zeros, y, M, IC, OC, G, workspace, ws_bytes, stream);
+    size_t need;
+    const int S = mxq_skinny_awq_slices(M, IC, OC, workspace ? ws_bytes : 0, &need);
+    if (S == 0) return MXQ_NOT_MY_SHAPE;
+    if (M <= 16) return launch_nj<1>(x, kernel, scales, zeros, y, M, IC, OC, G, workspace, S, stream);
+    return launch_nj<2>(x, kernel, scales, zeros, y, M, IC, OC, G, workspace, S, stream);
 }

@@ -35,36 +35,38 @@ POISON = 0xFF                          # 0xFFFF / 0xFFFFFFFF: NaN in fp16 and in
 
 
 class Carved:
-    """``nbytes`` of operand inside [guard | operand | guard], all three filled with ``POISON``."""
+    """``nbytes`` of operand inside [guard | operand | guard], all three filled with ``POISON``.  ``align``: the operand's
+    address modulo 16 is ``align % 16`` (16: 16-byte aligned), never 256-byte aligned."""
 
-    def __init__(self, nbytes: int, device, fill: int = POISON):
+    def __init__(self, nbytes: int, device, fill: int = POISON, align: int = 16):
         self.nbytes = int(nbytes)
-        self.base = torch.full((OPERAND_OFFSET + self.nbytes + GUARD_BYTES,), POISON, dtype=torch.uint8, device=device)
-        self.buf = self.base[OPERAND_OFFSET:OPERAND_OFFSET + self.nbytes]
+        self.offset = GUARD_BYTES + align
+        self.base = torch.full((self.offset + self.nbytes + GUARD_BYTES,), POISON, dtype=torch.uint8, device=device)
+        self.buf = self.base[self.offset:self.offset + self.nbytes]
         if fill != POISON:
             self.buf.fill_(fill)
         self.before: Optional[torch.Tensor] = None
-        assert self.ptr % 16 == 0 and self.ptr % 256 != 0, hex(self.ptr)
+        assert self.ptr % 16 == align % 16 and self.ptr % 256 != 0, hex(self.ptr)
 
     @classmethod
-    def copy_of(cls, t: torch.Tensor) -> "Carved":
+    def copy_of(cls, t: torch.Tensor, align: int = 16) -> "Carved":
         """A carved copy of ``t``'s bytes, remembered so that ``problems`` can tell whether the call changed them."""
         b = t.contiguous().reshape(-1).view(torch.uint8)
-        c = cls(b.numel(), t.device)
+        c = cls(b.numel(), t.device, align=align)
         c.buf.copy_(b)
         c.before = c.buf.clone()
         return c
 
     @property
     def ptr(self) -> int:
-        return self.base.data_ptr() + OPERAND_OFFSET
+        return self.base.data_ptr() + self.offset
 
     def view(self, dtype, shape) -> torch.Tensor:
         return self.buf.view(dtype).view(shape)
 
     def guard_damage(self) -> int:
         """Bytes of the two guards that no longer hold ``POISON``."""
-        lo, hi = self.base[:OPERAND_OFFSET], self.base[OPERAND_OFFSET + self.nbytes:]
+        lo, hi = self.base[:self.offset], self.base[self.offset + self.nbytes:]
         return int((lo != POISON).sum().item()) + int((hi != POISON).sum().item())
 
 
@@ -119,30 +121,36 @@ class GuardedLinear:
     def problems(self, lib=None, stream=None) -> List[str]:
         """Everything the call must have left as it was, or written; [] when all is well.  ``lib``: also ask
         mxq_workspace_status (device work: synchronises ``stream``)."""
-        out = []
         carved = {"x": self.x, "qweight": self.qweight, "rowmeta": self.rowmeta, "y": self.y}
-        if self.ws is not None:
-            carved["workspace"] = self.ws
         if self.scratch is not None:
             carved["scratch"] = self.scratch
-        for name, c in carved.items():
-            bad = c.guard_damage()
-            if bad:
-                out.append(f"{name}: {bad} guard bytes overwritten")
-            if c.before is not None and not torch.equal(c.buf, c.before):
-                out.append(f"{name}: input changed by the call")
-        nan = int(torch.isnan(self.y.view(torch.float16, (self.M, self.N))).sum().item())
-        if nan:
-            out.append(f"y: {nan} elements never written (still NaN)")
-        if self.ws is not None and self.ws.nbytes >= _lib.WS_HEAD_BYTES:
-            head = self.ws.buf[:_lib.WS_HEAD_BYTES]
-            if bool(head.any().item()):
-                out.append(f"workspace head not zero at bytes {torch.nonzero(head).flatten()[:8].tolist()}")
-            if lib is not None:
-                st = workspace_status(lib, self.ws, stream)
-                if any(st):
-                    out.append(f"mxq_workspace_status reports {st}")
-        return out
+        return call_problems(carved, self.y.view(torch.float16, (self.M, self.N)), self.ws, lib, stream)
+
+
+def call_problems(carved: Dict[str, Carved], y16: torch.Tensor, ws: Optional[Carved], lib=None, stream=None) -> List[str]:
+    """The checks of a guarded call: every carved operand's guards intact and its bytes unchanged where it is an input, no
+    NaN left in ``y16``, the workspace's head zero and (``lib``) mxq_workspace_status clean; [] when all is well."""
+    out = []
+    if ws is not None:
+        carved = dict(carved, workspace=ws)
+    for name, c in carved.items():
+        bad = c.guard_damage()
+        if bad:
+            out.append(f"{name}: {bad} guard bytes overwritten")
+        if c.before is not None and not torch.equal(c.buf, c.before):
+            out.append(f"{name}: input changed by the call")
+    nan = int(torch.isnan(y16).sum().item())
+    if nan:
+        out.append(f"y: {nan} elements never written (still NaN)")
+    if ws is not None and ws.nbytes >= _lib.WS_HEAD_BYTES:
+        head = ws.buf[:_lib.WS_HEAD_BYTES]
+        if bool(head.any().item()):
+            out.append(f"workspace head not zero at bytes {torch.nonzero(head).flatten()[:8].tolist()}")
+        if lib is not None:
+            st = workspace_status(lib, ws, stream)
+            if any(st):
+                out.append(f"mxq_workspace_status reports {st}")
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------

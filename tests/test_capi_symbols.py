@@ -122,6 +122,9 @@ def test_argument_validation_rejects_before_any_launch(lib):
     assert lib.mxq_gemm_awq_f16(P, P, P, P, P, 16, 4096, 4096, 128, Q, 1 << 20, None) == E_ALIGN  # workspace alignment
     assert lib.mxq_gemm_awq_f16(P, P, None, P, P, 16, 4096, 4096, 128, None, 0, None) == E_NULL
     assert lib.mxq_gemm_awq_f16(Q, P, P, P, P, 16, 4096, 4096, 128, None, 0, None) == E_ALIGN
+    assert lib.mxq_gemm_awq_f16(P, P + 4, P, P, P, 16, 4096, 4096, 128, None, 0, None) == E_ALIGN    # codes: 16-byte LDS-DMA
+    assert lib.mxq_gemm_awq_f16(P, P, P, P + 2, P, 16, 4096, 4096, 128, None, 0, None) == E_ALIGN    # zeros: dword loads
+    assert lib.mxq_gemm_awq_f16(P, P, P, P, P, 16, 131072, 65536, 65536, None, 0, None) == E_SHAPE  # IC * G > 2^32: inexact group index
     assert not hasattr(lib, "mxq_prefetch")                                           # round-2 experiment: a record, not ABI
     assert lib.mxq_gemv_proto_f16(P, P, P, P, P, P, P, P, P, 1, 2048, 4096, 16, None) == E_SHAPE   # IC must be 4096
     assert lib.mxq_gemm_workspace_bytes() == 64 * 1024 + 256 * 2 * 256 * 128 * 4 or lib.mxq_gemm_workspace_bytes() > 64 * 1024
