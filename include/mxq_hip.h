@@ -309,7 +309,10 @@ int mxq_gemv_staged_f16(const void* x_staged, const void* x_sum, const void* qwe
  * (device); cos/sin f32 [max_ctx][64]; out fp16 [heads*128].
  * Precondition: 0 <= *pos < max_ctx at the time the kernel runs (the caller tracks the position it increments
  * on the device, e.g. mxq_amd/llama_decode.py's ContextWindow).  A position outside the cache is not written
- * anywhere: that launch leaves the caches untouched and fills `out` with NaN. */
+ * anywhere: that launch leaves the caches untouched and fills `out` with NaN.
+ * Alignment, for this entry and the row / split forms below: both caches 16 bytes (their rows are read with 16-byte
+ * vector loads); pos 8; qkv and out 2 (element-wise accesses); the rotary tables and the rotary row 4.  max_ctx <= 32768;
+ * cache rows at and beyond *pos may hold anything, NaN included: they are loaded speculatively and never used. */
 int mxq_attn_decode_f16(const void* qkv, void* k_cache, void* v_cache, const void* pos, const void* cos_t,
                         const void* sin_t, void* out, int heads, int head_dim, int max_ctx, void* stream);
 
@@ -319,7 +322,9 @@ int mxq_attn_decode_f16(const void* qkv, void* k_cache, void* v_cache, const voi
  * load that depends on another load's result except the cache rows beyond the 64th key.  Same arithmetic, same results. */
 int mxq_rope_row_f32(const void* pos, const void* cos_t, const void* sin_t, void* row, int half_dim, int max_ctx, void* stream);
 /* ... and the token's embedding row in the same launch, for the stage that owns the embedding: h_out f16[hidden] =
- * embed f16[vocab, hidden][*token] (token int64[1] on the device, clamped into [0, vocab)), next to the rotary row. */
+ * embed f16[vocab, hidden][*token] (token int64[1] on the device, clamped into [0, vocab)), next to the rotary row.
+ * embed and h_out 16-byte aligned, hidden % 8 == 0; token and pos 8; the tables and the row 4.  Without a token
+ * (mxq_rope_row_f32) h_out is not touched. */
 int mxq_embed_rope_row(const void* token, const void* embed, int vocab, int hidden, void* h_out, const void* pos, const void* cos_t,
                        const void* sin_t, void* row, int half_dim, int max_ctx, void* stream);
 int mxq_attn_decode_row_f16(const void* qkv, void* k_cache, void* v_cache, const void* pos, const void* rope_row, void* out,
@@ -340,7 +345,8 @@ int mxq_attn_decode_split_f16(const void* qkv, void* k_cache, void* v_cache, con
  * Linear + greedy argmax of ONE token.  h fp16[K], norm_w fp16[K], w fp16[V, K] (row-major nn.Linear weight), K = 4096;
  * the normalised row is fp16(h * rsqrt(mean h^2 + eps)) * norm_w, a logit the fp32 dot rounded to fp16, the result
  * the lowest index of the largest logit (NaN logits never win), written to *token (int64, device).  part: scratch of
- * part_slots * 8 bytes (>= 256 slots recommended; fewer slots = fewer workgroups). */
+ * part_slots * 8 bytes (>= 256 slots recommended; fewer slots = fewer workgroups).  When every logit is NaN (a NaN in
+ * h) the result is token 0.  Alignment: h, norm_w and w 16 bytes; part 4; token 8 (as pos and generated below). */
 int mxq_lmhead_argmax_f16(const void* h, const void* norm_w, float eps, const void* w, int V, int K, void* part,
                           int part_slots, void* token, void* stream);
 /* The same, plus the token loop's bookkeeping in the second launch: the id is also stored at generated[*pos] (int64

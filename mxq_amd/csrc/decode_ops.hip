@@ -560,11 +560,18 @@ static size_t attn_smem(int max_ctx) { return (size_t)(3 * HD + max_ctx + 8 + 16
 
 // beyond 64 KiB the kernel needs the ceiling raised: set once per kernel and device to the CU's whole LDS, which bounds
 // every max_ctx (a larger request fails here, before the launch)
+// The ceiling covers the kernel's STATIC LDS as well (the split kernel's arrival flag): asking for all 160 KiB as dynamic LDS
+// on top of it is refused by the runtime, and the split entry then failed for every max_ctx beyond 13943.
 template <auto Kernel>
 static hipError_t attn_lds_ceiling(size_t smem) {
-    if (smem <= 64 * 1024) return hipSuccess;
-    if (smem > 160 * 1024) return hipErrorInvalidValue;
-    return mxq_set_dyn_lds_once<Kernel>(160 * 1024);
+    if (smem <= 60 * 1024) return hipSuccess;      // (ordinary caches: no query; the kernels' static LDS is a few bytes)
+    static const size_t fixed = [] {
+        hipFuncAttributes a{};
+        return hipFuncGetAttributes(&a, (const void*)Kernel) == hipSuccess ? (size_t)a.sharedSizeBytes : (size_t)0;
+    }();
+    if (smem + fixed <= 64 * 1024) return hipSuccess;
+    if (smem + fixed > 160 * 1024) return hipErrorInvalidValue;
+    return mxq_set_dyn_lds_once<Kernel>(160 * 1024 - (int)fixed);
 }
 
 template <bool ROW>

@@ -171,6 +171,20 @@ def reference(x16: torch.Tensor, w16: torch.Tensor) -> Tuple[torch.Tensor, torch
     return x @ w.t(), ((x * x) @ (w * w).t()).sqrt()
 
 
+def unrounded(p, layout: str) -> torch.Tensor:
+    """fp64 [N, K] s * (q - z) before the fp16 rounding: the weights the GEMV multiplies (csrc/gemv.hip, header)."""
+    from mxq_amd import packing
+    from oracle import mxq_oracle as O
+    if layout in ("mixed", "mixedc"):
+        params = {k: v.cpu().numpy() for k, v in packing.unpack(p).items()}
+        params.update(N=p.N, K=p.K)
+        return torch.from_numpy(O.mxq_dequant(params)).double().cuda()
+    _, c = packing.expand_uniform(p)
+    scale = (c["qs"].repeat_interleave(16, 0) * (c["sc"].float() - c["qz"].repeat_interleave(16, 0))).double()
+    per = p.K // scale.shape[1]
+    return (scale.repeat_interleave(per, 1) * (c["codes"].double() - c["zero"].double().repeat_interleave(per, 1)))
+
+
 def check_bound(y16: torch.Tensor, r: torch.Tensor, s: torch.Tensor, tau: float, what: str = "") -> float:
     """Assert, for every element,
 

@@ -50,17 +50,7 @@ def _weight(N, K, layout):
     return _CACHE[layout]
 
 
-def _unrounded(p, layout):
-    """fp64 [N, K] s * (q - z) before the fp16 rounding: the weights the GEMV multiplies (csrc/gemv.hip, header)."""
-    from mxq_amd import packing
-    if layout in ("mixed", "mixedc"):
-        params = {k: v.cpu().numpy() for k, v in packing.unpack(p).items()}
-        params.update(N=p.N, K=p.K)
-        return torch.from_numpy(O.mxq_dequant(params)).double().cuda()
-    _, c = packing.expand_uniform(p)
-    scale = (c["qs"].repeat_interleave(16, 0) * (c["sc"].float() - c["qz"].repeat_interleave(16, 0))).double()
-    per = p.K // scale.shape[1]
-    return (scale.repeat_interleave(per, 1) * (c["codes"].double() - c["zero"].double().repeat_interleave(per, 1)))
+_unrounded = LG.unrounded
 
 
 def _activations(M, N, K):
