@@ -247,6 +247,54 @@ int mxq_linear_grad_input_f16_sliced(const void* dy, const void* qweight, const 
                                      int K, int layout, int slices, void* workspace, size_t workspace_bytes,
                                      void* stream);
 
+/* ---- bf16 activations ("A16" is both 16-bit types) ----------------------------------------------------------------------
+ * The weight of a bf16 layer is W'_bf16 = bf16_RNE(fp32 s * (q - z)): the fp32 value of mxq_dequant_f16, rounded once to
+ * bf16 instead of fp16 (the reference's write-back casts to the layer's own dtype, mxqgpt.py:448); NaN stays NaN.  Layouts:
+ * MXQ_LAYOUT_MIXED and MXQ_LAYOUT_MIXEDC (another layout: MXQ_E_SHAPE).  x, y, dy, dx are bf16, row-major, contiguous;
+ * sums are fp32, results rounded once to bf16 (RNE).  Every entry validates first (NULL, then shape / layout, then 16-byte
+ * alignment), allocates nothing, never synchronises and can be captured in a graph.
+ *
+ * mxq_dequant_bf16: the dense bf16 [N, K] weight.  mxq_dense_bf16: mxq_dense_f16 on bf16 operands (bf16 builds of the same two
+ * kernels, same variants).  mxq_linear_grad_input_bf16 / _sliced: dx = dy . W'_bf16, the schedules, the workspace rule and
+ * mxq_linear_grad_input_workspace_need of the fp16 entries.
+ *
+ * mxq_linear_bf16_auto: y = x . W'_bf16^T, one dispatch rule (csrc/capi.hip plan_linear_bf16; the switch points are
+ * read off profiles/bf16_linear_bench.txt) over the fused dequant kernel of csrc/linear_bf16.hip and the hoisted mode:
+ *   - from mxq_linear_bf16_hoist_min_tokens() (129) tokens, given a scratch of mxq_hoist_scratch_bytes(N, K), and where the
+ *     128-token tiles number more than a sixth of the CUs (384 tokens at 4096 channels, 129 at 11008): HOISTED
+ *     (mxq_dequant_bf16 into the scratch, then mxq_dense_bf16 on it).  Below that token count no call hoists, so a caller
+ *     need not offer a scratch;
+ *   - up to 32 tokens the 32-token tile (NARROW), beyond it the 128-token tile (WIDE), 256 channels wide;
+ *   - where those tiles alone do not fill the chip and a workspace is given: the K range cut into S <= 16 slices of at least
+ *     four 64-deep steps (_SLICED), fp32 slabs [S][M][N] beyond the workspace head (never touched), summed in slice order by
+ *     a combine launch: deterministic.  Never sliced without a workspace.
+ * mxq_linear_bf16_schedule: the schedule a call runs (host-only).  mxq_linear_bf16_workspace_need: the bytes it uses given a
+ * full workspace: MXQ_WS_HEAD_BYTES + S * M * N * 4 where sliced, else 0.  mxq_linear_bf16_sched: one schedule by name (tests,
+ * A/B runs): a _SLICED schedule takes the plan's slice count, or two where the plan would not slice (MXQ_E_SHAPE if the
+ * workspace does not hold them, MXQ_E_NULL without one); HOISTED needs the scratch. */
+enum mxq_linear_bf16_sched {
+    MXQ_BF16_NARROW = 1,          /* 32-token tiles, whole K range per workgroup */
+    MXQ_BF16_NARROW_SLICED = 2,   /* ... K slices + combine launch */
+    MXQ_BF16_WIDE = 3,            /* 128-token tiles, whole K range per workgroup */
+    MXQ_BF16_WIDE_SLICED = 4,     /* ... K slices + combine launch */
+    MXQ_BF16_HOISTED = 5          /* mxq_dequant_bf16 into the scratch + mxq_dense_bf16 */
+};
+int mxq_dequant_bf16(const void* qweight, const void* rowmeta, void* w16, int N, int K, int layout, void* stream);
+int mxq_dense_bf16(const void* x, const void* w16, void* y, int M, int N, int K, int variant, void* stream);
+int mxq_linear_bf16_schedule(int M, int N, int K, int layout, size_t workspace_bytes, size_t scratch_bytes);
+size_t mxq_linear_bf16_workspace_need(int M, int N, int K, int layout, int hoisting);
+int mxq_linear_bf16_hoist_min_tokens(void);
+int mxq_linear_bf16_auto(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K, int layout,
+                         void* workspace, size_t workspace_bytes, void* bf16_scratch, size_t scratch_bytes, void* stream);
+int mxq_linear_bf16_sched(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K, int layout,
+                          int sched, void* workspace, size_t workspace_bytes, void* bf16_scratch, size_t scratch_bytes,
+                          void* stream);
+int mxq_linear_grad_input_bf16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                               int layout, void* workspace, size_t workspace_bytes, void* stream);
+int mxq_linear_grad_input_bf16_sliced(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N,
+                                      int K, int layout, int slices, void* workspace, size_t workspace_bytes,
+                                      void* stream);
+
 /* Uniform-bit-width layouts for the W2A16 / W4A16 / mixed sweep (BASELINE config 5); the mixed
  * layout is layout 0.  1 = W2G16: Quantizer(bits=2, qq_scale_bits=4) on every 16-column group
  * (quantizer.py:61-147), 4.5 bit/weight; 2 = W4ROW: Quantizer(bits=4, qq_scale_bits=4) per row

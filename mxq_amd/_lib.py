@@ -21,6 +21,8 @@ WS_HEAD_BYTES, WS_MAILBOX_OFFSET, WS_STATUS_OFFSET = 65536, 65504, 65520
 SCHED_NAMES = {1: "gemv", 2: "skinny", 3: "midm", 4: "fused64_streamk", 5: "fused64_slices", 6: "fused128_streamk",
                7: "fused128_slices", 8: "fused128n64_streamk", 9: "fused128n64_slices", 10: "fused256", 11: "tile128",
                12: "hoisted"}
+# mxq_linear_bf16_schedule's result: include/mxq_hip.h enum mxq_linear_bf16_sched
+BF16_SCHED_NAMES = {1: "narrow", 2: "narrow_sliced", 3: "wide", 4: "wide_sliced", 5: "hoisted"}
 # mxq_gemm_awq_schedule's result: include/mxq_hip.h enum mxq_awq_sched
 AWQ_SCHED_NAMES = {1: "skinny", 2: "skinny_sliced", 3: "fused64_slices", 4: "fused64_streamk", 5: "fused64", 6: "fused128_slices",
                    7: "fused128_streamk", 8: "fused256"}
@@ -95,6 +97,18 @@ SIGNATURES = {
     "mxq_gemm_awq_f16": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "mxq_gemm_awq_schedule": (c_int, [c_int, c_int, c_int, c_int, c_size_t]),
     "mxq_gemm_awq_workspace_need": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "mxq_dequant_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mxq_dense_bf16": (c_int, [c_void_p] * 3 + [c_int, c_int, c_int, c_int, c_void_p]),
+    "mxq_linear_bf16_schedule": (c_int, [c_int, c_int, c_int, c_int, c_size_t, c_size_t]),
+    "mxq_linear_bf16_workspace_need": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "mxq_linear_bf16_hoist_min_tokens": (c_int, []),
+    "mxq_linear_bf16_auto": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t,
+                                     c_void_p]),
+    "mxq_linear_bf16_sched": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
+                                      c_size_t, c_void_p]),
+    "mxq_linear_grad_input_bf16": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "mxq_linear_grad_input_bf16_sliced": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                                                                  c_void_p]),
     "mxq_gemv_proto_f16": (c_int, [c_void_p] * 9 + [c_int, c_int, c_int, c_int, c_void_p]),
 }
 

@@ -92,6 +92,14 @@ int mxq_dequant_f16_compact(const void* qweight, const void* rowmeta, void* w16,
     return mxq_launch_dequant_f16(qweight, rowmeta, w16, N, K, 1, (hipStream_t)stream);
 }
 
+// the same weight rounded once to bf16 instead of fp16 (layout MXQ_LAYOUT_MIXED or MXQ_LAYOUT_MIXEDC)
+int mxq_dequant_bf16(const void* qweight, const void* rowmeta, void* w16, int N, int K, int layout, void* stream) {
+    if (!qweight || !rowmeta || !w16) return MXQ_E_NULL;
+    if (!shape_ok(N, K) || !mxq_layout_is_mixed(layout)) return MXQ_E_SHAPE;
+    if (!aligned16(qweight) || !aligned16(rowmeta) || !aligned16(w16)) return MXQ_E_ALIGN;
+    return mxq_launch_dequant_bf16(qweight, rowmeta, w16, N, K, layout == MXQ_LAYOUT_MIXEDC, (hipStream_t)stream);
+}
+
 static int linear_check(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K) {
     if (!x || !qweight || !rowmeta || !y) return MXQ_E_NULL;
     if (!shape_ok(N, K) || M <= 0) return MXQ_E_SHAPE;
@@ -491,6 +499,129 @@ int mxq_linear_grad_input_f16_sliced(const void* dy, const void* qweight, const 
     return mxq_launch_gemm_dx_f16(dy, qweight, rowmeta, dx, M, N, K, layout,
                                   slices > 1 ? (char*)workspace + MXQ_WS_HEAD_BYTES : nullptr, slices,
                                   (hipStream_t)stream);
+}
+
+int mxq_linear_grad_input_bf16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                               int layout, void* workspace, size_t workspace_bytes, void* stream) {
+    const size_t need = mxq_linear_grad_input_workspace_need(M, N, K, layout);
+    if (const int e = grad_input_check(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, need)) return e;
+    const int S = workspace ? mxq_gemm_dx_slices(M, N, K, grad_input_slab_bytes(workspace_bytes)) : 1;
+    return mxq_launch_gemm_dx_bf16(dy, qweight, rowmeta, dx, M, N, K, layout,
+                                   S > 1 ? (char*)workspace + MXQ_WS_HEAD_BYTES : nullptr, S, (hipStream_t)stream);
+}
+
+int mxq_linear_grad_input_bf16_sliced(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N,
+                                      int K, int layout, int slices, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+    if (slices > 1 && !workspace) return MXQ_E_NULL;
+    const size_t need = slices > 1 && M > 0 && K > 0 ? MXQ_WS_HEAD_BYTES + (size_t)slices * M * K * 4 : 0;
+    if (const int e = grad_input_check(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, need)) return e;
+    if (slices < 1 || slices > 64) return MXQ_E_SHAPE;
+    return mxq_launch_gemm_dx_bf16(dy, qweight, rowmeta, dx, M, N, K, layout,
+                                   slices > 1 ? (char*)workspace + MXQ_WS_HEAD_BYTES : nullptr, slices,
+                                   (hipStream_t)stream);
+}
+
+// ---- the quantised Linear on bf16 activations: ONE dispatch rule (include/mxq_hip.h, enum mxq_linear_bf16_sched) ------------
+// y = x . w16^T on a dense bf16 weight: the variants of mxq_dense_f16 on the bf16 builds of the two dense kernels
+static int dense_bf16(const void* x, const void* w16, void* y, int M, int N, int K, int variant, hipStream_t stream) {
+    if (variant != 1) {
+        const int e = mxq_launch_dense256_bf16(x, w16, y, M, N, K, variant == 2, stream);
+        if (e != MXQ_NOT_MY_SHAPE) return e;
+        if (variant == 2) return MXQ_E_SHAPE;
+    }
+    return mxq_launch_gemm8b_dense_bf16(x, w16, y, M, N, K, stream);
+}
+
+int mxq_dense_bf16(const void* x, const void* w16, void* y, int M, int N, int K, int variant, void* stream) {
+    if (!x || !w16 || !y) return MXQ_E_NULL;
+    if (M < 0 || !shape_ok(N, K)) return MXQ_E_SHAPE;
+    if (!aligned16(x) || !aligned16(w16) || !aligned16(y)) return MXQ_E_ALIGN;
+    if (variant < 0 || variant > 2) return MXQ_E_SHAPE;
+    if (M == 0) return 0;
+    return dense_bf16(x, w16, y, M, N, K, variant, (hipStream_t)stream);
+}
+
+// Where the plan switches, read off profiles/bf16_linear_bench.txt (tools/bf16_linear_bench.py; tests/test_bf16_perf.py holds
+// "auto" within 15 % of the fastest forced schedule).  Up to BF16_NARROW_MAX tokens the 32-token tile: one tile row holds every
+// token, and sliced it leads the 128-token tile at 32 tokens at all three Llama shapes (28 / 30, 41 / 57, 39 / 44 us); from 48
+// tokens (two rows) it is level or behind (34 / 35, 65 / 63, 55 / 47 us).  Given a scratch, the dequant pass + the dense
+// kernels from BF16_HOIST_MIN tokens on wherever mxq_linear_bf16_hoists says that the sliced 128-token tiles have fallen
+// behind (csrc/linear_bf16.hip: it depends on the tile count, not on the tokens alone).
+static const int BF16_NARROW_MAX = 32, BF16_HOIST_MIN = 129;
+
+static LinearPlan plan_linear_bf16(int M, int N, int K, size_t ws_bytes, size_t scratch_bytes) {
+    if (M >= BF16_HOIST_MIN && scratch_bytes >= (size_t)N * K * 2 && mxq_linear_bf16_hoists(M, N)) return {MXQ_BF16_HOISTED, 0};
+    const bool narrow = M <= BF16_NARROW_MAX;
+    const int S = ws_bytes > MXQ_WS_HEAD_BYTES ? mxq_linear_bf16_slices(narrow ? 32 : 128, M, N, K, ws_bytes - MXQ_WS_HEAD_BYTES) : 1;
+    if (S > 1) return {narrow ? MXQ_BF16_NARROW_SLICED : MXQ_BF16_WIDE_SLICED, MXQ_WS_HEAD_BYTES + (size_t)S * M * N * 4};
+    return {narrow ? MXQ_BF16_NARROW : MXQ_BF16_WIDE, 0};
+}
+
+// validation of the bf16 Linear family: NULL, then shapes and the layout, then alignment
+static int linear_bf16_check(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K, int layout,
+                             const void* workspace, const void* scratch) {
+    if (!x || !qweight || !rowmeta || !y) return MXQ_E_NULL;
+    if (!shape_ok(N, K) || M <= 0 || !mxq_layout_is_mixed(layout)) return MXQ_E_SHAPE;
+    if (!aligned16(x) || !aligned16(qweight) || !aligned16(rowmeta) || !aligned16(y)) return MXQ_E_ALIGN;
+    if ((workspace && !aligned16(workspace)) || (scratch && !aligned16(scratch))) return MXQ_E_ALIGN;
+    return 0;
+}
+
+static int run_plan_bf16(int sched, const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K,
+                         int layout, void* ws, size_t ws_bytes, void* scratch, size_t scratch_bytes, bool forced,
+                         hipStream_t st) {
+    if (sched == MXQ_BF16_HOISTED) {
+        if (!scratch) return MXQ_E_NULL;
+        if (scratch_bytes < (size_t)N * K * 2) return MXQ_E_SHAPE;
+        if (const int e = mxq_launch_dequant_bf16(qweight, rowmeta, scratch, N, K, layout == MXQ_LAYOUT_MIXEDC, st)) return e;
+        return dense_bf16(x, scratch, y, M, N, K, 0, st);
+    }
+    const int bm = sched == MXQ_BF16_NARROW || sched == MXQ_BF16_NARROW_SLICED ? 32 : 128;
+    int S = 1;
+    if (sched == MXQ_BF16_NARROW_SLICED || sched == MXQ_BF16_WIDE_SLICED) {
+        if (!ws) return MXQ_E_NULL;
+        const size_t slab = ws_bytes > MXQ_WS_HEAD_BYTES ? ws_bytes - MXQ_WS_HEAD_BYTES : 0;
+        S = mxq_linear_bf16_slices(bm, M, N, K, slab);
+        // a forced sliced schedule where the plan would not slice: two slices (a slice past the last K-step sums nothing)
+        if (S < 2 && forced && slab / ((size_t)M * N * 4) >= 2) S = 2;
+        if (S < 2) return MXQ_E_SHAPE;
+    }
+    return mxq_launch_linear_bf16(x, qweight, rowmeta, y, M, N, K, layout, bm, S > 1 ? (char*)ws + MXQ_WS_HEAD_BYTES : nullptr, S,
+                                  st);
+}
+
+int mxq_linear_bf16_schedule(int M, int N, int K, int layout, size_t workspace_bytes, size_t scratch_bytes) {
+    if (!shape_ok(N, K) || M <= 0 || !mxq_layout_is_mixed(layout)) return MXQ_E_SHAPE;
+    return plan_linear_bf16(M, N, K, workspace_bytes, scratch_bytes).sched;
+}
+
+size_t mxq_linear_bf16_workspace_need(int M, int N, int K, int layout, int hoisting) {
+    if (!shape_ok(N, K) || M <= 0 || !mxq_layout_is_mixed(layout)) return 0;
+    return plan_linear_bf16(M, N, K, mxq_gemm8_workspace_bytes(), hoisting ? (size_t)N * K * 2 : 0).ws_need;
+}
+
+int mxq_linear_bf16_hoist_min_tokens(void) { return BF16_HOIST_MIN; }
+
+int mxq_linear_bf16_auto(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K, int layout,
+                         void* workspace, size_t workspace_bytes, void* bf16_scratch, size_t scratch_bytes, void* stream) {
+    if (const int e = linear_bf16_check(x, qweight, rowmeta, y, M, N, K, layout, workspace, bf16_scratch)) return e;
+    if (!workspace) workspace_bytes = 0;
+    if (!bf16_scratch) scratch_bytes = 0;
+    const LinearPlan p = plan_linear_bf16(M, N, K, workspace_bytes, scratch_bytes);
+    return run_plan_bf16(p.sched, x, qweight, rowmeta, y, M, N, K, layout, workspace, workspace_bytes, bf16_scratch, scratch_bytes,
+                         false, (hipStream_t)stream);
+}
+
+int mxq_linear_bf16_sched(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K, int layout,
+                          int sched, void* workspace, size_t workspace_bytes, void* bf16_scratch, size_t scratch_bytes,
+                          void* stream) {
+    if (const int e = linear_bf16_check(x, qweight, rowmeta, y, M, N, K, layout, workspace, bf16_scratch)) return e;
+    if (sched < MXQ_BF16_NARROW || sched > MXQ_BF16_HOISTED) return MXQ_E_SHAPE;
+    if (!workspace) workspace_bytes = 0;
+    if (!bf16_scratch) scratch_bytes = 0;
+    return run_plan_bf16(sched, x, qweight, rowmeta, y, M, N, K, layout, workspace, workspace_bytes, bf16_scratch, scratch_bytes,
+                         true, (hipStream_t)stream);
 }
 
 // hipStreamGetCaptureInfo through THIS library's HIP runtime (the process's own: a caller that dlopens "libamdhip64.so" by

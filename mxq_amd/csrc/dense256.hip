@@ -28,6 +28,19 @@
 #include "mxq_dequant.h"
 #include "mxq_kernels.h"
 
+// The element type is a build parameter: this file is compiled twice.  dense256.hip itself: fp16.  dense256_bf16.hip
+// (#defines MXQ_D256_BF16 and includes this file): bf16 operands and result, v_mfma_f32_16x16x32_bf16 -- the tiles, the
+// phases and the LDS-DMA are the same code (both types are 2 bytes; the MFMAs run at the same rate).
+#ifdef MXQ_D256_BF16
+#define D256_BF16 true
+#define D256_KERNEL mxq_dense256_bf16_kernel
+#define D256_LAUNCH mxq_launch_dense256_bf16
+#else
+#define D256_BF16 false
+#define D256_KERNEL mxq_dense256_f16_kernel
+#define D256_LAUNCH mxq_launch_dense256_f16
+#endif
+
 namespace {
 
 constexpr int BM = 256, BN = 256, BK = 64, THREADS = 512;
@@ -111,7 +124,7 @@ __device__ __forceinline__ void mfma_quadrant(f32x4 (&acc)[4][8], const WFrag& w
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                acc[WS * 2 + i][XS * 4 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[kk][i], xf[kk][j], acc[WS * 2 + i][XS * 4 + j], 0, 0, 0);
+                acc[WS * 2 + i][XS * 4 + j] = mfma16x32<D256_BF16>(wf[kk][i], xf[kk][j], acc[WS * 2 + i][XS * 4 + j]);
 }
 
 // One wave's two pieces (8 rows x 128 B each) of unit KIND of K-tile kt (of the tile behind `s`) into LDS slot `slot`
@@ -134,8 +147,8 @@ __device__ __forceinline__ void store_tile(const f32x4 (&acc)[4][8], uint16_t* _
         uint32_t c[4][2];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            c[i][0] = mxq_pack_f16(acc[i][j][0], acc[i][j][1]);
-            c[i][1] = mxq_pack_f16(acc[i][j][2], acc[i][j][3]);
+            c[i][0] = mxq_pack16<D256_BF16>(acc[i][j][0], acc[i][j][1]);
+            c[i][1] = mxq_pack16<D256_BF16>(acc[i][j][2], acc[i][j][3]);
         }
 #pragma unroll
         for (int d = 0; d < 2; ++d) {
@@ -207,7 +220,7 @@ __device__ __forceinline__ void pair(Regs& R, char* smem, const Src& cur, const 
     phase<7, LAST>(R, smem, cur, nxt, voff, kt0, wave, wr, wc, fr, fq);
 }
 
-__global__ __launch_bounds__(THREADS) void mxq_dense256_f16_kernel(const uint16_t* __restrict__ x,
+__global__ __launch_bounds__(THREADS) void D256_KERNEL(const uint16_t* __restrict__ x,
                                                                    const uint16_t* __restrict__ w,
                                                                    uint16_t* __restrict__ y, int M, int N, int K,
                                                                    int tiles_m, int tiles_n, int tiles, int grid) {
@@ -275,7 +288,7 @@ __global__ __launch_bounds__(THREADS) void mxq_dense256_f16_kernel(const uint16_
 
 // -> 0 launched; MXQ_NOT_MY_SHAPE: the shape is not this kernel's (K-tile count odd or < 2, rows beyond the 32-bit descriptor offsets, or
 // -- unless force -- a tile count that fills the chip too unevenly): the caller takes the 256 x 128 kernel
-int mxq_launch_dense256_f16(const void* x, const void* w16, void* y, int M, int N, int K, int force, hipStream_t stream) {
+int D256_LAUNCH(const void* x, const void* w16, void* y, int M, int N, int K, int force, hipStream_t stream) {
     if (K % (2 * BK) != 0 || K < 2 * BK || (int64_t)BM * K * 2 >= ((int64_t)1 << 32)) return MXQ_NOT_MY_SHAPE;
     const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN, tiles = tiles_m * tiles_n;
     const int cus = mxq_cu_count() / 8 * 8;   // whole XCDs (tile_of)
@@ -287,15 +300,15 @@ int mxq_launch_dense256_f16(const void* x, const void* w16, void* y, int M, int 
         const double e128 = (double)t128 / ((double)((t128 + cus - 1) / cus) * cus);
         if (1.17 * e256 < e128) return MXQ_NOT_MY_SHAPE;
     }
-    hipError_t e = mxq_set_dyn_lds_once<&mxq_dense256_f16_kernel>(SMEM);
+    hipError_t e = mxq_set_dyn_lds_once<&D256_KERNEL>(SMEM);
     if (e != hipSuccess) return (int)e;
     const int grid = tiles < cus ? tiles : cus;
-    mxq_dense256_f16_kernel<<<grid, THREADS, SMEM, stream>>>((const uint16_t*)x, (const uint16_t*)w16, (uint16_t*)y, M, N, K,
+    D256_KERNEL<<<grid, THREADS, SMEM, stream>>>((const uint16_t*)x, (const uint16_t*)w16, (uint16_t*)y, M, N, K,
                                                             tiles_m, tiles_n, tiles, grid);
     return (int)hipGetLastError();
 }
 
-#ifdef MXQ_PROFILING
+#if defined(MXQ_PROFILING) && !defined(MXQ_D256_BF16)
 extern "C" int mxq_prof_dense256_f16(const void* x, const void* w16, void* y, int M, int N, int K, void* stream_) {
     return mxq_launch_dense256_f16(x, w16, y, M, N, K, 1, (hipStream_t)stream_);
 }

@@ -67,7 +67,12 @@ namespace {
 // MXQ_G8_AWQ (gemm8a.hip, gemm8aq.hip): the same kernel with dequant waves for the OPERANDS of the reference's
 // gemm_forward_cuda (K-major 4-bit words, group-wise fp16 scales, packed integer zero-points: "AWQ layout" below) instead of
 // the MXQ block formats -- one more build of this file, whose kernels take three more arguments.
-#if defined(MXQ_G8_AWQ) && MXQ_G8_BM == 256
+// MXQ_G8_BF16 (gemm8b.hip): the 256-token build's DENSE mode alone (the hoisted mode's 256 x 128-tile kernel) on bf16 operands:
+// the MFMA and the output pack are swapped, the tiles, rings and LDS-DMA are the same code; no dequant-wave kernel is built.
+#if defined(MXQ_G8_BF16)
+#define G8_NAME(stem) mxq_##stem##gemm8b
+#define G8_BF16 true
+#elif defined(MXQ_G8_AWQ) && MXQ_G8_BM == 256
 #define G8_NAME(stem) mxq_##stem##gemm8a
 #elif defined(MXQ_G8_AWQ) && MXQ_G8_BM == 128
 #define G8_NAME(stem) mxq_##stem##gemm8ah
@@ -87,7 +92,12 @@ namespace {
 #define G8_CAT_(a, b) a##b
 #define G8_CAT(a, b) G8_CAT_(a, b)
 #define G8_SYM(stem, suffix) G8_CAT(G8_NAME(stem), suffix)
+#ifdef G8_BF16
+#define G8_KERNEL G8_SYM(, _bf16_kernel)
+#else
 #define G8_KERNEL G8_SYM(, _f16_kernel)
+#define G8_BF16 false
+#endif
 constexpr int BM = MXQ_G8_BM, BN = MXQ_G8_BN, BK = 64;
 static_assert(BN == 128 || (BN == 64 && BM <= 128), "tile width");
 static_assert(BM == 256 || BM == 128 || BM == 64, "tile height");
@@ -264,7 +274,7 @@ __device__ __forceinline__ void mfma_rows(AccT& acc, const Frag4& wf, const Frag
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             if constexpr (ABL & ABL_NO_MFMA) asm volatile("" ::"v"(wf[i]), "v"(xf[j]));
-            else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[i], xf[j], acc[i][j], 0, 0, 0);
+            else acc[i][j] = mfma16x32<G8_BF16>(wf[i], xf[j], acc[i][j]);
             if constexpr (FILLN > 0) {
 #pragma unroll
                 for (int q = 0; q < FILLN; ++q) fl->f[(j * FILLN + q) & 3] += 1.5f;
@@ -396,8 +406,8 @@ __device__ __forceinline__ void store_block_xpose(const f32x4 (&c4)[4], uint16_t
     uint32_t c[4][2];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        c[i][0] = mxq_pack_f16(c4[i][0], c4[i][1]);
-        c[i][1] = mxq_pack_f16(c4[i][2], c4[i][3]);
+        c[i][0] = mxq_pack16<G8_BF16>(c4[i][0], c4[i][1]);
+        c[i][1] = mxq_pack16<G8_BF16>(c4[i][2], c4[i][3]);
     }
 #pragma unroll
     for (int d = 0; d < 2; ++d) {
@@ -1727,6 +1737,12 @@ static int launch8_slices(const void* x, const void* qweight, const void* rowmet
 
 }   // namespace
 
+#if defined(MXQ_G8_BF16)
+// hoisted-dequant mode in bf16: w16 = dense bf16 [N, K] weight (mxq_dequant_bf16's output); whole tiles, no workspace
+int G8_SYM(launch_, _dense_bf16)(const void* x, const void* w16, void* y, int M, int N, int K, hipStream_t stream) {
+    return launch8<0, LAYOUT_DENSE16>(x, w16, nullptr, y, M, N, K, nullptr, 0, false, stream);
+}
+#else
 // the stream-K grid's workspace: the head, then two fp32 partial tiles per workgroup (one per CU of whole XCDs)
 size_t G8_SYM(, _workspace_bytes)() { return MXQ_WS_HEAD_BYTES + (size_t)(mxq_cu_count() / 8 * 8) * 2 * BM * BN * sizeof(float); }
 
@@ -1790,6 +1806,7 @@ int G8_SYM(launch_, _dense_f16)(const void* x, const void* w16, void* y, int M, 
 #endif
 
 #endif   // !MXQ_G8_AWQ
+#endif   // !MXQ_G8_BF16
 
 #if defined(MXQ_PROFILING) && !defined(MXQ_G8_AWQ)
 // Built only into libmxq_hip_prof.so (make prof; tools/): parts of the kernel removed to time the rest.

@@ -1,5 +1,7 @@
 // Input gradient of the quantised Linear: dx[M, K] = dy[M, N] . W'[N, K], W' the bit-exact dequantised weight of a
-// packed MXQ tensor (mixed layout, exact or compact metadata), fp32 accumulation, fp16 result (RNE).
+// packed MXQ tensor (mixed layout, exact or compact metadata), fp32 accumulation, fp16 result (RNE).  The element type is a
+// template parameter: BF16 = true reads dy as bf16, rounds W' once to bf16 (mxq_dequant_bf16's weight), multiplies with
+// v_mfma_f32_16x16x32_bf16 and rounds dx to bf16 -- the same schedules, the same workspace rule.
 //
 // The reduction runs over the weight's ROWS (N) and the output over its columns (K): dy is the MFMA A operand (its
 // reduction axis is contiguous, like x in the forward) and W' the B operand, which needs a column of W' per lane.  The
@@ -50,7 +52,7 @@ constexpr int DX_Y_BYTES = DX_BM * DX_Y_STRIDE;      // 18432
 
 __device__ __forceinline__ int w_swz(int r) { return 2 * ((r & 3) | ((r >> 1) & 4)); }
 
-template <bool COMPACT, bool SLICED>
+template <bool COMPACT, bool SLICED, bool BF16>
 __global__ __launch_bounds__(DX_THREADS) void mxq_gemm_dx_kernel(const uint16_t* __restrict__ dy,
                                                                      const uint32_t* __restrict__ qweight,
                                                                      const float4* __restrict__ rowmeta,
@@ -139,10 +141,10 @@ __global__ __launch_bounds__(DX_THREADS) void mxq_gemm_dx_kernel(const uint16_t*
                     const float z = F::z2(t, qt, r);
                     const uint32_t scw = F::scw(t, r);
                     const float qs = __uint_as_float(t[F::qq(qt)]), qz = __uint_as_float(t[F::qq(qt) + 1]);
-                    mxq_deq2x8(d, h, mxq_scale(qs, qz, (scw >> (4 * qt)) & 15u), z, o);
+                    mxq_deq2x8<BF16>(d, h, mxq_scale(qs, qz, (scw >> (4 * qt)) & 15u), z, o);
                 } else {
                     const float4 rm = ((const float4*)(raw_lds + 16 * BLK_U4))[nl];
-                    mxq_deq4x8(t[mxq_c4(h, r)], mxq_scale(rm.z, rm.w, (uint32_t)rm.y), rm.x, o);
+                    mxq_deq4x8<BF16>(t[mxq_c4(h, r)], mxq_scale(rm.z, rm.w, (uint32_t)rm.y), rm.x, o);
                 }
             }
             const int ch = cl * 8 + slot;
@@ -171,7 +173,7 @@ __global__ __launch_bounds__(DX_THREADS) void mxq_gemm_dx_kernel(const uint16_t*
                     if (i * 16 >= m_rows) break;                  // wave-uniform: token sub-tiles past M
                     const half8 af = *(const half8*)(y_lds + (wm * 64 + i * 16 + (lane & 15)) * DX_Y_STRIDE + kk * 64 + 16 * g);
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf[j], acc[i][j], 0, 0, 0);
+                    for (int j = 0; j < 4; ++j) acc[i][j] = mfma16x32<BF16>(af, bf[j], acc[i][j]);
                 }
             }
         }
@@ -192,15 +194,15 @@ __global__ __launch_bounds__(DX_THREADS) void mxq_gemm_dx_kernel(const uint16_t*
                 if constexpr (SLICED) {
                     slab[((int64_t)slice * M + m) * K + k] = acc[i][j][e];
                 } else {
-                    const _Float16 hv = (_Float16)acc[i][j][e];
-                    dx[(int64_t)m * K + k] = __builtin_bit_cast(uint16_t, hv);
+                    dx[(int64_t)m * K + k] = f2e<BF16>(acc[i][j][e]);
                 }
             }
         }
     }
 }
 
-// dx = fp16(sum over z in order of slab[z]), four elements per thread (M * K % 4 == 0: K % 64 == 0)
+// dx = fp16 / bf16 (sum over z in order of slab[z]), four elements per thread (M * K % 4 == 0: K % 64 == 0)
+template <bool BF16>
 __global__ __launch_bounds__(256) void mxq_gemm_dx_combine_kernel(const float4* __restrict__ slab, uint2* __restrict__ dx,
                                                                   int64_t n4, int S) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -210,26 +212,26 @@ __global__ __launch_bounds__(256) void mxq_gemm_dx_combine_kernel(const float4* 
         const float4 b = slab[(int64_t)z * n4 + i];
         a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
     }
-    dx[i] = make_uint2(mxq_pack_f16(a.x, a.y), mxq_pack_f16(a.z, a.w));
+    dx[i] = make_uint2(mxq_pack16<BF16>(a.x, a.y), mxq_pack16<BF16>(a.z, a.w));
 }
 
-template <bool COMPACT>
+template <bool COMPACT, bool BF16>
 int launch(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K, void* slab, int S,
            hipStream_t stream) {
     const int tiles_k = (K + DX_BK - 1) / DX_BK, tiles = ((M + DX_BM - 1) / DX_BM) * tiles_k;
     const int steps = (N + DX_BN - 1) / DX_BN;
     if (S <= 1) {
-        mxq_gemm_dx_kernel<COMPACT, false><<<dim3(tiles), DX_THREADS, 0, stream>>>(
+        mxq_gemm_dx_kernel<COMPACT, false, BF16><<<dim3(tiles), DX_THREADS, 0, stream>>>(
             (const uint16_t*)dy, (const uint32_t*)qweight, (const float4*)rowmeta, (uint16_t*)dx, nullptr, M, N, K,
             tiles_k, steps);
         return (int)hipGetLastError();
     }
     const int per = (steps + S - 1) / S;
-    mxq_gemm_dx_kernel<COMPACT, true><<<dim3(tiles, S), DX_THREADS, 0, stream>>>(
+    mxq_gemm_dx_kernel<COMPACT, true, BF16><<<dim3(tiles, S), DX_THREADS, 0, stream>>>(
         (const uint16_t*)dy, (const uint32_t*)qweight, (const float4*)rowmeta, nullptr, (float*)slab, M, N, K, tiles_k,
         per);
     const int64_t n4 = (int64_t)M * K / 4;
-    mxq_gemm_dx_combine_kernel<<<dim3((unsigned)((n4 + 255) / 256)), 256, 0, stream>>>((const float4*)slab, (uint2*)dx,
+    mxq_gemm_dx_combine_kernel<BF16><<<dim3((unsigned)((n4 + 255) / 256)), 256, 0, stream>>>((const float4*)slab, (uint2*)dx,
                                                                                        n4, S);
     return (int)hipGetLastError();
 }
@@ -251,6 +253,12 @@ int mxq_gemm_dx_slices(int M, int N, int K, size_t slab_bytes) {
 
 int mxq_launch_gemm_dx_f16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
                            int layout, void* slab, int slices, hipStream_t stream) {
-    return layout == MXQ_LAYOUT_MIXEDC ? launch<true>(dy, qweight, rowmeta, dx, M, N, K, slab, slices, stream)
-                                       : launch<false>(dy, qweight, rowmeta, dx, M, N, K, slab, slices, stream);
+    return layout == MXQ_LAYOUT_MIXEDC ? launch<true, false>(dy, qweight, rowmeta, dx, M, N, K, slab, slices, stream)
+                                       : launch<false, false>(dy, qweight, rowmeta, dx, M, N, K, slab, slices, stream);
+}
+
+int mxq_launch_gemm_dx_bf16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                            int layout, void* slab, int slices, hipStream_t stream) {
+    return layout == MXQ_LAYOUT_MIXEDC ? launch<true, true>(dy, qweight, rowmeta, dx, M, N, K, slab, slices, stream)
+                                       : launch<false, true>(dy, qweight, rowmeta, dx, M, N, K, slab, slices, stream);
 }

@@ -1,5 +1,5 @@
 // gfx950 building blocks shared by the kernel units: vector types, buffer descriptors, the 16-byte LDS-DMA, the LDS
-// swizzle of 128-byte rows, the lane id, v_and_or_b32 and fp16 <-> fp32 on raw bits.  Device code only; the host-side
+// swizzle of 128-byte rows, the lane id, v_and_or_b32, fp16 <-> fp32 on raw bits and the 16x16x32 MFMA of either 16-bit type.  Device code only; the host-side
 // format headers (mxq_format.h, mxq_pack.h, mxq_dequant.h) do not include it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -9,6 +9,7 @@ namespace {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -42,6 +43,27 @@ __device__ __forceinline__ float h2f(uint16_t h) { return (float)__builtin_bit_c
 __device__ __forceinline__ uint16_t f2h(float f) {
     const _Float16 h = (_Float16)f;
     return __builtin_bit_cast(uint16_t, h);
+}
+
+// fp32 -> the bits of the 16-bit element type, RNE: fp16 (BF16 = false) or bf16 (NaN stays NaN)
+template <bool BF16>
+__device__ __forceinline__ uint16_t f2e(float f) {
+    if constexpr (BF16) {
+        const __bf16 b = (__bf16)f;
+        return __builtin_bit_cast(uint16_t, b);
+    } else {
+        return f2h(f);
+    }
+}
+
+// c += a . b, one 16 x 16 x 32 MFMA on 8 fp16 (BF16 = false) or 8 bf16 values per lane (both carried as half8 bit patterns):
+// v_mfma_f32_16x16x32_f16 / v_mfma_f32_16x16x32_bf16, the same rate
+template <bool BF16>
+__device__ __forceinline__ f32x4 mfma16x32(half8 a, half8 b, f32x4 c) {
+    if constexpr (BF16)
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }
 
 }   // namespace

@@ -1,7 +1,9 @@
 // Register-level dequantisation helpers (packed codes -> fp16 pairs), bit-exact with the
 // reference's fp32 formula  w' = scale * (q - zero)  rounded once to fp16
 // (reference mxq_quant/lib/quantizer.py:19-20, mxqgpt.py:448), where
-// scale = qs * (scale_code - qz) (quantizer.py:121).
+// scale = qs * (scale_code - qz) (quantizer.py:121).  The same helpers with BF16 = true round that
+// fp32 value once to bf16 instead (the write-back into a bf16 layer, mxqgpt.py:448): the LUT and the
+// byte selections do not depend on the 16-bit element type, only the pack does.
 //
 // A 2-bit group has only four possible values, so it is dequantised through a 4-entry
 // fp16 LUT computed in fp32 and selected with v_perm_b32 on the
@@ -21,6 +23,11 @@ MXQ_HD uint32_t mxq_pack_f16(float a, float b) {
     h2 v = {(_Float16)a, (_Float16)b};   // RNE (default float mode)
     return __builtin_bit_cast(uint32_t, v);
 }
+MXQ_HD uint32_t mxq_pack_bf16(float a, float b) {
+    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
+    b2 v = {(__bf16)a, (__bf16)b};       // v_cvt_pk_bf16_f32: RNE, NaN stays NaN
+    return __builtin_bit_cast(uint32_t, v);
+}
 #else
 // host emulation of v_perm_b32: selector byte 0..3 -> bytes of `lo`, 4..7 -> bytes of `hi`
 static inline uint32_t mxq_perm_emu(uint32_t hi, uint32_t lo, uint32_t sel) {
@@ -38,15 +45,29 @@ uint16_t mxq_host_f32_to_f16(float f);   // provided by the host harness (RNE)
 MXQ_HD uint32_t mxq_pack_f16(float a, float b) {
     return (uint32_t)mxq_host_f32_to_f16(a) | ((uint32_t)mxq_host_f32_to_f16(b) << 16);
 }
+// fp32 -> bf16, round to nearest even; NaN stays a (quiet) NaN
+static inline uint32_t mxq_host_f32_to_bf16(float f) {
+    uint32_t u;
+    __builtin_memcpy(&u, &f, 4);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (u >> 16) | 0x40u;
+    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+MXQ_HD uint32_t mxq_pack_bf16(float a, float b) { return mxq_host_f32_to_bf16(a) | (mxq_host_f32_to_bf16(b) << 16); }
 #endif
+// the pair pack of the element type: fp16 (BF16 = false) or bf16
+template <bool BF16>
+MXQ_HD uint32_t mxq_pack16(float a, float b) {
+    return BF16 ? mxq_pack_bf16(a, b) : mxq_pack_f16(a, b);
+}
 
 // scale from its 4-bit code: fp32 qs * (code - qz), one rounding per op
 MXQ_HD float mxq_scale(float qs, float qz, uint32_t code) { return qs * ((float)code - qz); }
 
-// 16 two-bit codes (byte-spread word d) -> 8 x packed fp16 pairs, out[i] = elements (2i, 2i+1)
+// 16 two-bit codes (byte-spread word d) -> 8 x packed fp16 (bf16) pairs, out[i] = elements (2i, 2i+1)
+template <bool BF16 = false>
 MXQ_HD void mxq_deq2x16(uint32_t d, float s, float z, uint32_t out[8]) {
-    const uint32_t p01 = mxq_pack_f16(s * (0.0f - z), s * (1.0f - z));
-    const uint32_t p23 = mxq_pack_f16(s * (2.0f - z), s * (3.0f - z));
+    const uint32_t p01 = mxq_pack16<BF16>(s * (0.0f - z), s * (1.0f - z));
+    const uint32_t p23 = mxq_pack16<BF16>(s * (2.0f - z), s * (3.0f - z));
     const uint32_t lut_lo = MXQ_PERM(p23, p01, 0x06040200u);   // low bytes of e0..e3
     const uint32_t lut_hi = MXQ_PERM(p23, p01, 0x07050301u);   // high bytes of e0..e3
 #pragma unroll
@@ -60,9 +81,10 @@ MXQ_HD void mxq_deq2x16(uint32_t d, float s, float z, uint32_t out[8]) {
 }
 
 // ... and one half of them: elements 8h .. 8h+7 -> 4 x packed fp16 pairs (the same LUT, the same selections)
+template <bool BF16 = false>
 MXQ_HD void mxq_deq2x8(uint32_t d, int h, float s, float z, uint32_t out[4]) {
-    const uint32_t p01 = mxq_pack_f16(s * (0.0f - z), s * (1.0f - z));
-    const uint32_t p23 = mxq_pack_f16(s * (2.0f - z), s * (3.0f - z));
+    const uint32_t p01 = mxq_pack16<BF16>(s * (0.0f - z), s * (1.0f - z));
+    const uint32_t p23 = mxq_pack16<BF16>(s * (2.0f - z), s * (3.0f - z));
     const uint32_t lut_lo = MXQ_PERM(p23, p01, 0x06040200u);
     const uint32_t lut_hi = MXQ_PERM(p23, p01, 0x07050301u);
 #pragma unroll
@@ -94,13 +116,14 @@ MXQ_HD float mxq_ubyte3(uint32_t v) { return (float)(v >> 24); }
 #endif
 
 // 8 four-bit codes (byte-spread word d) -> 4 x packed fp16 pairs
+template <bool BF16 = false>
 MXQ_HD void mxq_deq4x8(uint32_t d, float s, float z, uint32_t out[4]) {
     const uint32_t m0 = d & 0x0F0F0F0Fu;          // elements 0..3, one per byte
     const uint32_t m1 = (d >> 4) & 0x0F0F0F0Fu;   // elements 4..7
-    out[0] = mxq_pack_f16(s * (mxq_ubyte0(m0) - z), s * (mxq_ubyte1(m0) - z));
-    out[1] = mxq_pack_f16(s * (mxq_ubyte2(m0) - z), s * (mxq_ubyte3(m0) - z));
-    out[2] = mxq_pack_f16(s * (mxq_ubyte0(m1) - z), s * (mxq_ubyte1(m1) - z));
-    out[3] = mxq_pack_f16(s * (mxq_ubyte2(m1) - z), s * (mxq_ubyte3(m1) - z));
+    out[0] = mxq_pack16<BF16>(s * (mxq_ubyte0(m0) - z), s * (mxq_ubyte1(m0) - z));
+    out[1] = mxq_pack16<BF16>(s * (mxq_ubyte2(m0) - z), s * (mxq_ubyte3(m0) - z));
+    out[2] = mxq_pack16<BF16>(s * (mxq_ubyte0(m1) - z), s * (mxq_ubyte1(m1) - z));
+    out[3] = mxq_pack16<BF16>(s * (mxq_ubyte2(m1) - z), s * (mxq_ubyte3(m1) - z));
 }
 
 // Integer unpack (the bit-exact contract of the unpack kernel)

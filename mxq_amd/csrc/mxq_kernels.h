@@ -18,6 +18,8 @@ int mxq_launch_unpack(const void* qweight, const void* rowmeta, uint8_t* codes2,
                       int N, int K, int compact, hipStream_t stream);   // compact: the qweight is in MXQ_LAYOUT_MIXEDC
 int mxq_launch_dequant_f16(const void* qweight, const void* rowmeta, void* out, int N, int K, int compact,
                            hipStream_t stream);
+int mxq_launch_dequant_bf16(const void* qweight, const void* rowmeta, void* out, int N, int K, int compact,
+                            hipStream_t stream);   // the same fp32 s * (q - z), rounded once to bf16
 int mxq_launch_compact(const void* qweight_exact, void* qweight_compact, int N, int K, hipStream_t stream);
 int mxq_launch_quantize_pack(const void* W, int dtype, const uint8_t* dead, void* qweight, void* rowmeta, int N,
                              int K, hipStream_t stream);
@@ -208,3 +210,15 @@ int mxq_launch_gemv_proto_f16(const void* x, const void* weight, const void* wei
 int mxq_gemm_dx_slices(int M, int N, int K, size_t slab_bytes);
 int mxq_launch_gemm_dx_f16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
                            int layout, void* slab, int slices, hipStream_t stream);
+int mxq_launch_gemm_dx_bf16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                            int layout, void* slab, int slices, hipStream_t stream);   // the same kernel on bf16 dy / W' / dx
+// linear_bf16.hip: the quantised Linear on bf16 activations (mixed layout, exact or compact metadata); bm = 128 | 32: the
+// token tile; `slices` <= 1: one launch of whole tiles, else `slices` K-slices into fp32 slabs at `slab` (slices * M * N * 4
+// bytes) and a combine launch.  mxq_linear_bf16_slices: the slices that fill the chip with `slab_bytes` of slab (1: none)
+int mxq_linear_bf16_slices(int bm, int M, int N, int K, size_t slab_bytes);
+bool mxq_linear_bf16_hoists(int M, int N);     // the measured switch to the hoisted mode (more than one 128-token tile row)
+int mxq_launch_linear_bf16(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K, int layout,
+                           int bm, void* slab, int slices, hipStream_t stream);
+// the dense kernels on bf16 operands (dense256_bf16.hip, gemm8b.hip): as mxq_launch_dense256_f16 / mxq_launch_gemm8_dense_f16
+int mxq_launch_dense256_bf16(const void* x, const void* w16, void* y, int M, int N, int K, int force, hipStream_t stream);
+int mxq_launch_gemm8b_dense_bf16(const void* x, const void* w16, void* y, int M, int N, int K, hipStream_t stream);

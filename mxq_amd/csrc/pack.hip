@@ -93,10 +93,9 @@ __global__ void mxq_unpack_kernel(const uint32_t* __restrict__ qweight, const fl
 // pieces of 16 different rows per instruction: 13.0 -> 9.6 us at 4096^2, profiles/r03_dense256.txt.)
 // Block = 4 waves = the 4 chunks of a chunk quad x one 16-row block; a wave does its chunk's rows 0-7, then 8-15.
 // ------------------------------------------------------------------------------------ //
-template <bool COMPACT>
-__global__ __launch_bounds__(256) void mxq_dequant_f16_kernel(const uint32_t* __restrict__ qweight,
-                                                              const float4* __restrict__ rowmeta,
-                                                              uint16_t* __restrict__ out, int N, int K) {
+template <bool COMPACT, bool BF16>
+__device__ __forceinline__ void dequant_rows(const uint32_t* __restrict__ qweight, const float4* __restrict__ rowmeta,
+                                             uint16_t* __restrict__ out, int N, int K) {
     const int NC = K / 64, NC4 = (NC + 3) / 4;
     const int rb = blockIdx.x / NC4, c4 = blockIdx.x % NC4;
     const int lane = threadIdx.x & 63;
@@ -114,13 +113,28 @@ __global__ __launch_bounds__(256) void mxq_dequant_f16_kernel(const uint32_t* __
             const float z = F::z2(tile, qt, r);
             const uint32_t scw = F::scw(tile, r);
             const float qs = __uint_as_float(tile[F::qq(qt)]), qz = __uint_as_float(tile[F::qq(qt) + 1]);
-            mxq_deq2x8(d, h, mxq_scale(qs, qz, (scw >> (4 * qt)) & 15u), z, o);
+            mxq_deq2x8<BF16>(d, h, mxq_scale(qs, qz, (scw >> (4 * qt)) & 15u), z, o);
         } else {
             const float4 m = rowmeta[n];
-            mxq_deq4x8(tile[mxq_c4(h, r)], mxq_scale(m.z, m.w, (uint32_t)m.y), m.x, o);
+            mxq_deq4x8<BF16>(tile[mxq_c4(h, r)], mxq_scale(m.z, m.w, (uint32_t)m.y), m.x, o);
         }
         *(uint4*)(out + (int64_t)n * K + c * 64 + slot * 8) = make_uint4(o[0], o[1], o[2], o[3]);
     }
+}
+
+template <bool COMPACT>
+__global__ __launch_bounds__(256) void mxq_dequant_f16_kernel(const uint32_t* __restrict__ qweight,
+                                                              const float4* __restrict__ rowmeta,
+                                                              uint16_t* __restrict__ out, int N, int K) {
+    dequant_rows<COMPACT, false>(qweight, rowmeta, out, N, K);
+}
+
+// ... and to a dense bf16 [N, K] matrix: the same fp32 s * (q - z), rounded once to bf16 (the write-back into a bf16 layer)
+template <bool COMPACT>
+__global__ __launch_bounds__(256) void mxq_dequant_bf16_kernel(const uint32_t* __restrict__ qweight,
+                                                               const float4* __restrict__ rowmeta,
+                                                               uint16_t* __restrict__ out, int N, int K) {
+    dequant_rows<COMPACT, true>(qweight, rowmeta, out, N, K);
 }
 
 // ------------------------------------------------------------------------------------ //
@@ -567,6 +581,18 @@ int mxq_launch_dequant_f16(const void* qweight, const void* rowmeta, void* out, 
     else
         mxq_dequant_f16_kernel<false><<<grid, 256, 0, stream>>>((const uint32_t*)qweight, (const float4*)rowmeta,
                                                                 (uint16_t*)out, N, K);
+    return (int)hipGetLastError();
+}
+
+int mxq_launch_dequant_bf16(const void* qweight, const void* rowmeta, void* out, int N, int K, int compact,
+                            hipStream_t stream) {
+    const unsigned grid = (unsigned)((N / 16) * ((K / 64 + 3) / 4));
+    if (compact)
+        mxq_dequant_bf16_kernel<true><<<grid, 256, 0, stream>>>((const uint32_t*)qweight, (const float4*)rowmeta,
+                                                                (uint16_t*)out, N, K);
+    else
+        mxq_dequant_bf16_kernel<false><<<grid, 256, 0, stream>>>((const uint32_t*)qweight, (const float4*)rowmeta,
+                                                                 (uint16_t*)out, N, K);
     return (int)hipGetLastError();
 }
 

@@ -239,6 +239,8 @@ def workspace_status(device: Optional[torch.device] = None, reset: bool = True) 
         with torch.cuda.device(dev_index):
             torch.cuda.synchronize(dev_index)          # (capture workspaces have no eager stream of their own)
             for ws in workspaces:
+                if not ws.head_ready:       # a capture workspace handed out with counters=False only: no stream-K launch
+                    continue                # has seen it and its head was never written -- there is no status in it
                 _lib.check(lib.mxq_workspace_status(ws.buf.data_ptr(), ws.buf.numel(), ctypes.cast(st, ctypes.c_void_p), None),
                            "mxq_workspace_status")
                 if st[0] != 0:
@@ -408,6 +410,19 @@ def dequant(p: PackedMXQ) -> torch.Tensor:
     return out
 
 
+def dequant_bf16(p: PackedMXQ) -> torch.Tensor:
+    """Dense bf16 [N, K] fake-quant weight: the fp32 s * (q - z) of ``dequant`` rounded once to bf16 (bit-identical to the
+    reference's write-back into a bf16 layer)."""
+    if not isinstance(p, PackedMXQ):
+        raise ValueError("dequant_bf16 needs a PackedMXQ weight (mixed layout, exact or compact metadata)")
+    _need_gpu(p.qweight)
+    out = torch.empty((p.N, p.K), dtype=torch.bfloat16, device=p.device)
+    with _on_device(p.device):
+        _lib.check(_lib.load().mxq_dequant_bf16(p.qweight.data_ptr(), p.rowmeta.data_ptr(), out.data_ptr(), p.N, p.K,
+                                                _layout_code(p), _stream(out)), "mxq_dequant_bf16")
+    return out
+
+
 DENSE_VARIANTS = {"auto": 0, "dense128": 1, "dense256": 2}   # include/mxq_hip.h: mxq_dense_f16 variants
 
 
@@ -434,6 +449,31 @@ def linear_dense(x: torch.Tensor, w16: torch.Tensor, out: Optional[torch.Tensor]
         with _on_device(x.device):
             _lib.check(_lib.load().mxq_dense_f16(x2.data_ptr(), w16.data_ptr(), out.data_ptr(), M, N, K,
                                                  DENSE_VARIANTS[variant], _stream(x2)), f"mxq_dense_f16[{variant}]")
+    return out.reshape(*x.shape[:-1], N)
+
+
+def linear_dense_bf16(x: torch.Tensor, w16: torch.Tensor, out: Optional[torch.Tensor] = None, variant: str = "auto") -> torch.Tensor:
+    """``linear_dense`` on bf16 operands: y = x @ w16.T for bf16 x [..., K] and a dense bf16 [N, K] weight (e.g.
+    ``dequant_bf16(p)``), fp32 accumulation, bf16 result; the bf16 builds of the same two kernels, the same variants."""
+    _need_gpu(x, w16)
+    if x.dtype != torch.bfloat16 or w16.dtype != torch.bfloat16 or w16.dim() != 2 or x.shape[-1] != w16.shape[1]:
+        raise ValueError("expected bf16 x [..., K] and bf16 w16 [N, K]")
+    if not w16.is_contiguous():
+        raise ValueError("w16 must be contiguous")
+    if variant not in DENSE_VARIANTS:
+        raise ValueError(f"unknown variant {variant!r}")
+    N, K = w16.shape
+    check_shape(N, K)
+    x2 = x.reshape(-1, K).contiguous()
+    M = x2.shape[0]
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    elif out.shape != (M, N) or out.dtype != torch.bfloat16 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous bfloat16 [tokens, out_features] tensor")
+    if M:
+        with _on_device(x.device):
+            _lib.check(_lib.load().mxq_dense_bf16(x2.data_ptr(), w16.data_ptr(), out.data_ptr(), M, N, K,
+                                                  DENSE_VARIANTS[variant], _stream(x2)), f"mxq_dense_bf16[{variant}]")
     return out.reshape(*x.shape[:-1], N)
 
 
@@ -571,6 +611,103 @@ def linear_grad_input(dy: torch.Tensor, p: PackedMXQ, out: Optional[torch.Tensor
             rc = lib.mxq_linear_grad_input_f16_sliced(*args, S, ws.data_ptr() if ws is not None else None,
                                                       ws.numel() if ws is not None else 0, st)
         _lib.check(rc, f"linear_grad_input[{path}]")
+    return out.reshape(*dy.shape[:-1], p.K)
+
+
+BF16_PATHS = {"narrow": 1, "narrow_sliced": 2, "wide": 3, "wide_sliced": 4, "hoisted": 5}   # enum mxq_linear_bf16_sched
+
+
+def linear_bf16(x: torch.Tensor, p: PackedMXQ, out: Optional[torch.Tensor] = None, path: str = "auto") -> torch.Tensor:
+    """y = x @ W.T for x [..., K] bf16 -> [..., N] bf16 (fp32 accumulation), W = ``dequant_bf16(p)`` of a PackedMXQ (exact or
+    compact metadata), computed by the fused dequant kernel without materialising W, or -- many tokens -- by the hoisted
+    mode (include/mxq_hip.h: mxq_linear_bf16_auto).
+
+    path: "auto" (the library's dispatch, with a workspace sized by mxq_linear_bf16_workspace_need and a scratch from
+    mxq_linear_bf16_hoist_min_tokens() tokens on), or one schedule by name (BF16_PATHS, enum mxq_linear_bf16_sched: tests
+    and A/B runs; a sliced schedule whose slabs do not fit the workspace raises ValueError)."""
+    if not isinstance(p, PackedMXQ):
+        raise ValueError("linear_bf16 needs a PackedMXQ weight (mixed layout, exact or compact metadata)")
+    _need_gpu(x, p.qweight)
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"activations must be bfloat16, got {x.dtype}")
+    if x.dim() < 1 or x.shape[-1] != p.K:
+        raise ValueError(f"in_features mismatch: x has {x.shape[-1] if x.dim() else None}, weight has {p.K}")
+    if x.device != p.qweight.device:
+        raise ValueError("x and the packed weight live on different devices")
+    if path != "auto" and path not in BF16_PATHS:
+        raise ValueError(f"unknown path {path!r}")
+    x2 = x.reshape(-1, p.K).contiguous()
+    M = x2.shape[0]
+    if out is None:
+        out = torch.empty((M, p.N), dtype=torch.bfloat16, device=x.device)
+    elif out.shape != (M, p.N) or out.dtype != torch.bfloat16 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous bfloat16 [tokens, out_features] tensor")
+    if M == 0:
+        return out.reshape(*x.shape[:-1], p.N)
+    lib = _lib.load()
+    lay = _layout_code(p)
+    args = (x2.data_ptr(), p.qweight.data_ptr(), p.rowmeta.data_ptr(), out.data_ptr(), M, p.N, p.K, lay)
+    st = _stream(x2)
+    with _on_device(x.device):
+        if path == "auto":
+            hoist = M >= lib.mxq_linear_bf16_hoist_min_tokens()
+            ws = gemm_workspace(x2.device, counters=False, stream=st,
+                                need=lib.mxq_linear_bf16_workspace_need(M, p.N, p.K, lay, int(hoist)))
+            scratch = hoist_scratch(x2.device, lib.mxq_hoist_scratch_bytes(p.N, p.K)) if hoist else None
+            rc = lib.mxq_linear_bf16_auto(*args, ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0,
+                                          scratch.data_ptr() if scratch is not None else None,
+                                          scratch.numel() if scratch is not None else 0, st)
+        else:
+            ws = gemm_workspace(x2.device, counters=False, stream=st) if path.endswith("_sliced") else None
+            scratch = hoist_scratch(x2.device, lib.mxq_hoist_scratch_bytes(p.N, p.K)) if path == "hoisted" else None
+            rc = lib.mxq_linear_bf16_sched(*args, BF16_PATHS[path], ws.data_ptr() if ws is not None else None,
+                                           ws.numel() if ws is not None else 0,
+                                           scratch.data_ptr() if scratch is not None else None,
+                                           scratch.numel() if scratch is not None else 0, st)
+        _lib.check(rc, f"linear_bf16[{path}]")
+    return out.reshape(*x.shape[:-1], p.N)
+
+
+def linear_grad_input_bf16(dy: torch.Tensor, p: PackedMXQ, out: Optional[torch.Tensor] = None, path: str = "auto") -> torch.Tensor:
+    """dx = dy @ W for dy [..., N] bf16 -> [..., K] bf16 (fp32 accumulation), W = ``dequant_bf16(p)``: the input gradient of
+    ``linear_bf16`` (include/mxq_hip.h: mxq_linear_grad_input_bf16).  path as in ``linear_grad_input``."""
+    if not isinstance(p, PackedMXQ):
+        raise ValueError("linear_grad_input_bf16 needs a PackedMXQ weight (mixed layout, exact or compact metadata)")
+    _need_gpu(dy, p.qweight)
+    if dy.dtype != torch.bfloat16:
+        raise ValueError(f"gradients must be bfloat16, got {dy.dtype}")
+    if dy.dim() < 1 or dy.shape[-1] != p.N:
+        raise ValueError(f"out_features mismatch: dy has {dy.shape[-1] if dy.dim() else None}, weight has {p.N}")
+    if dy.device != p.qweight.device:
+        raise ValueError("dy and the packed weight live on different devices")
+    if path not in GRAD_INPUT_PATHS:
+        raise ValueError(f"unknown path {path!r}")
+    dy2 = dy.reshape(-1, p.N).contiguous()
+    M = dy2.shape[0]
+    if out is None:
+        out = torch.empty((M, p.K), dtype=torch.bfloat16, device=dy.device)
+    elif out.shape != (M, p.K) or out.dtype != torch.bfloat16 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous bfloat16 [tokens, in_features] tensor")
+    if M == 0:
+        return out.reshape(*dy.shape[:-1], p.K)
+    lib = _lib.load()
+    lay = _layout_code(p)
+    args = (dy2.data_ptr(), p.qweight.data_ptr(), p.rowmeta.data_ptr(), out.data_ptr(), M, p.N, p.K, lay)
+    st = _stream(dy2)
+    with _on_device(dy.device):
+        if path == "auto":
+            ws = gemm_workspace(dy2.device, counters=False, stream=st,
+                                need=lib.mxq_linear_grad_input_workspace_need(M, p.N, p.K, lay))
+            rc = lib.mxq_linear_grad_input_bf16(*args, ws.data_ptr() if ws is not None else None,
+                                                ws.numel() if ws is not None else 0, st)
+        else:
+            S = 1 if path == "single" else grad_input_slices(M, p.N, p.K)
+            if path == "slices" and S < 2:
+                raise ValueError(f"the slices of {M} tokens x {p.K} columns do not fit the workspace")
+            ws = gemm_workspace(dy2.device, counters=False, stream=st) if S > 1 else None
+            rc = lib.mxq_linear_grad_input_bf16_sliced(*args, S, ws.data_ptr() if ws is not None else None,
+                                                       ws.numel() if ws is not None else 0, st)
+        _lib.check(rc, f"linear_grad_input_bf16[{path}]")
     return out.reshape(*dy.shape[:-1], p.K)
 
 

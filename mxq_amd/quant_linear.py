@@ -9,6 +9,9 @@ around its CUDA prototype; this is the module the name
 state_dict: ``qweight`` int32 [N/16 * K/64 * 144] (format version 1, exact metadata) or [N/16 * K/64 * 120]
 (version 2, compact metadata: fp16 zero-points, 3.75 bit/weight), ``rowmeta`` float32 [N, 4],
 ``fmt`` int32 [3] = (format version, N, K), optional ``bias`` float16 [N].
+
+Activations are fp16 or bf16 ("A16"): the module routes by ``x.dtype``.  In bf16 the weight is the same fp32 s * (q - z)
+rounded once to bf16 (what the reference writes back into a bf16 layer), and results and input gradients are bf16.
 """
 from __future__ import annotations
 
@@ -21,19 +24,28 @@ from . import packing
 
 
 class _QuantLinearFn(torch.autograd.Function):
-    """y = x W^T through the packed weight, differentiable in x alone: the forward is exactly ``packing.linear``, the
-    backward dx = dy W runs the fused dequant kernel (packing.linear_grad_input).  No activation is saved -- dx needs the
-    packed weight only -- and the weight's buffers get no gradient (frozen packed base)."""
+    """y = x W^T through the packed weight, differentiable in x alone: the forward is exactly ``packing.linear`` (bf16 x:
+    ``packing.linear_bf16``), the backward dx = dy W runs the fused dequant kernel (packing.linear_grad_input /
+    linear_grad_input_bf16) and returns dx in dy's dtype.  No activation is saved -- dx needs the packed weight only -- and
+    the weight's buffers get no gradient (frozen packed base)."""
 
     @staticmethod
     def forward(ctx, x: torch.Tensor, mod: "QuantLinear") -> torch.Tensor:
         ctx.mod = mod
-        return packing.linear(x, mod.packed())
+        return _linear(x, mod.packed())
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy: torch.Tensor):
+        if dy.dtype == torch.bfloat16:
+            return packing.linear_grad_input_bf16(dy, ctx.mod.packed()), None
         return packing.linear_grad_input(dy, ctx.mod.packed()), None
+
+
+def _linear(x: torch.Tensor, p: packing.PackedMXQ) -> torch.Tensor:
+    """The forward by activation dtype: bf16 -> packing.linear_bf16; everything else -> packing.linear (fp16; it rejects the
+    rest with ValueError)."""
+    return packing.linear_bf16(x, p) if x.dtype == torch.bfloat16 else packing.linear(x, p)
 
 
 class QuantLinear(nn.Module):
@@ -90,17 +102,22 @@ class QuantLinear(nn.Module):
     def packed(self) -> packing.PackedMXQ:
         return packing.PackedMXQ(self.qweight, self.rowmeta, self.out_features, self.in_features, self.compact)
 
-    def dequantize(self) -> torch.Tensor:
-        """fp16 [out, in] weight, bit-identical to the reference's fake-quant write-back."""
+    def dequantize(self, dtype: torch.dtype = torch.float16) -> torch.Tensor:
+        """fp16 (or, ``dtype=torch.bfloat16``, bf16) [out, in] weight, bit-identical to the reference's fake-quant write-back
+        into a layer of that dtype."""
+        if dtype == torch.bfloat16:
+            return packing.dequant_bf16(self.packed())
+        if dtype != torch.float16:
+            raise ValueError(f"dequantize: dtype must be torch.float16 or torch.bfloat16, got {dtype}")
         return packing.dequant(self.packed())
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if torch.is_grad_enabled() and x.requires_grad:
             y = _QuantLinearFn.apply(x, self)
         else:
-            y = packing.linear(x, self.packed())
+            y = _linear(x, self.packed())
         if self.bias is not None:
-            y = y + self.bias
+            y = y + self.bias.to(x.dtype)
         return y
 
     def extra_repr(self) -> str:
