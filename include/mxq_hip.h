@@ -295,6 +295,50 @@ int mxq_linear_grad_input_bf16_sliced(const void* dy, const void* qweight, const
                                       int K, int layout, int slices, void* workspace, size_t workspace_bytes,
                                       void* stream);
 
+/* ---- the input gradient at training token counts: the hoisted schedule ----------------------------------------------------
+ * From a few hundred tokens on the fused dX kernel re-dequantises every weight tile once per 128 tokens and falls behind a
+ * dense product.  The hoisted schedule dequantises ONCE, transposed, and lets the dense MFMA kernels stream the result.
+ *
+ * mxq_dequant_t_f16 / _bf16 (csrc/dequant_t.hip): wt16 = W'^T as a contiguous 16-bit [K, N] matrix, every element bit-identical
+ * to what mxq_dequant_f16 / mxq_dequant_f16_compact / mxq_dequant_bf16 write at [n, k].  Any N % 16 == 0, K % 64 == 0; layout
+ * MXQ_LAYOUT_MIXED or MXQ_LAYOUT_MIXEDC (another layout: MXQ_E_SHAPE).
+ *
+ * mxq_linear_grad_input_f16_hoisted / _bf16_hoisted: mxq_dequant_t_* into `scratch` (>= mxq_hoist_scratch_bytes(N, K) = 2 N K
+ * bytes, 16-byte aligned, overwritten; transient: nothing is cached between calls), then mxq_dense_f16 / mxq_dense_bf16 with
+ * x = dy [M, N] and w16 = W'^T [K, N]: dx [M, K], bit-identical to that dense call.  The dense kernels reduce in 64-deep
+ * steps, so the schedule exists where N % 64 == 0 (else MXQ_E_SHAPE).  No workspace is read or written; deterministic.
+ * Checks in the family's order: MXQ_E_NULL (an operand or the scratch), MXQ_E_SHAPE (M <= 0, N % 64, K % 64, the layout, a
+ * scratch of fewer than 2 N K bytes), MXQ_E_ALIGN.
+ *
+ * mxq_linear_grad_input_schedule: the ONE rule that names the schedule a call of this shape runs given a workspace of
+ * `workspace_bytes` and a scratch of `scratch_bytes` (0: none), or MXQ_E_SHAPE; host-only.  HOISTED where the scratch holds
+ * 2 N K bytes, N % 64 == 0, M >= mxq_linear_grad_input_hoist_min_tokens() and the measured condition of csrc/capi.hip
+ * (grad_input_hoists; profiles/grad_input_hoisted_bench.txt) holds; else SLICED where mxq_linear_grad_input_f16 would split
+ * the N reduction with that workspace, else SINGLE.
+ *
+ * mxq_linear_grad_input_f16_auto / _bf16_auto: the entry that dispatches on that rule -- mxq_linear_grad_input_f16 / _bf16
+ * (same checks, same results; exactly those entries when `scratch` is NULL) plus the hoisted schedule when a scratch is
+ * given.  A too small scratch never fails: the fused kernel runs instead.  A misaligned scratch is MXQ_E_ALIGN. */
+enum mxq_grad_input_sched {
+    MXQ_GRAD_INPUT_SINGLE = 1,    /* csrc/gemm_dx.hip: one launch of whole tiles */
+    MXQ_GRAD_INPUT_SLICED = 2,    /* ... the N reduction in slices + a combine launch */
+    MXQ_GRAD_INPUT_HOISTED = 3    /* mxq_dequant_t_* into the scratch + the dense kernels */
+};
+int mxq_dequant_t_f16(const void* qweight, const void* rowmeta, void* wt16, int N, int K, int layout, void* stream);
+int mxq_dequant_t_bf16(const void* qweight, const void* rowmeta, void* wt16, int N, int K, int layout, void* stream);
+int mxq_linear_grad_input_f16_hoisted(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                                      int layout, void* scratch, size_t scratch_bytes, void* stream);
+int mxq_linear_grad_input_bf16_hoisted(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                                       int layout, void* scratch, size_t scratch_bytes, void* stream);
+int mxq_linear_grad_input_schedule(int M, int N, int K, int layout, size_t workspace_bytes, size_t scratch_bytes);
+int mxq_linear_grad_input_hoist_min_tokens(void);
+int mxq_linear_grad_input_f16_auto(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                                   int layout, void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes,
+                                   void* stream);
+int mxq_linear_grad_input_bf16_auto(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                                    int layout, void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes,
+                                    void* stream);
+
 /* Uniform-bit-width layouts for the W2A16 / W4A16 / mixed sweep (BASELINE config 5); the mixed
  * layout is layout 0.  1 = W2G16: Quantizer(bits=2, qq_scale_bits=4) on every 16-column group
  * (quantizer.py:61-147), 4.5 bit/weight; 2 = W4ROW: Quantizer(bits=4, qq_scale_bits=4) per row

@@ -23,6 +23,8 @@ SCHED_NAMES = {1: "gemv", 2: "skinny", 3: "midm", 4: "fused64_streamk", 5: "fuse
                12: "hoisted"}
 # mxq_linear_bf16_schedule's result: include/mxq_hip.h enum mxq_linear_bf16_sched
 BF16_SCHED_NAMES = {1: "narrow", 2: "narrow_sliced", 3: "wide", 4: "wide_sliced", 5: "hoisted"}
+# mxq_linear_grad_input_schedule's result: include/mxq_hip.h enum mxq_grad_input_sched
+GRAD_INPUT_SCHED_NAMES = {1: "single", 2: "sliced", 3: "hoisted"}
 # mxq_gemm_awq_schedule's result: include/mxq_hip.h enum mxq_awq_sched
 AWQ_SCHED_NAMES = {1: "skinny", 2: "skinny_sliced", 3: "fused64_slices", 4: "fused64_streamk", 5: "fused64", 6: "fused128_slices",
                    7: "fused128_streamk", 8: "fused256"}
@@ -109,6 +111,16 @@ SIGNATURES = {
     "mxq_linear_grad_input_bf16": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "mxq_linear_grad_input_bf16_sliced": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
                                                                   c_void_p]),
+    "mxq_dequant_t_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mxq_dequant_t_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mxq_linear_grad_input_f16_hoisted": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "mxq_linear_grad_input_bf16_hoisted": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "mxq_linear_grad_input_schedule": (c_int, [c_int, c_int, c_int, c_int, c_size_t, c_size_t]),
+    "mxq_linear_grad_input_hoist_min_tokens": (c_int, []),
+    "mxq_linear_grad_input_f16_auto": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
+                                               c_size_t, c_void_p]),
+    "mxq_linear_grad_input_bf16_auto": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
+                                                c_size_t, c_void_p]),
     "mxq_gemv_proto_f16": (c_int, [c_void_p] * 9 + [c_int, c_int, c_int, c_int, c_void_p]),
 }
 

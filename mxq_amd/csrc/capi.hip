@@ -100,6 +100,21 @@ int mxq_dequant_bf16(const void* qweight, const void* rowmeta, void* w16, int N,
     return mxq_launch_dequant_bf16(qweight, rowmeta, w16, N, K, layout == MXQ_LAYOUT_MIXEDC, (hipStream_t)stream);
 }
 
+// W'^T as a dense [K, N] matrix, element for element the bits of mxq_dequant_f16 / _bf16 (csrc/dequant_t.hip)
+int mxq_dequant_t_f16(const void* qweight, const void* rowmeta, void* wt16, int N, int K, int layout, void* stream) {
+    if (!qweight || !rowmeta || !wt16) return MXQ_E_NULL;
+    if (!shape_ok(N, K) || !mxq_layout_is_mixed(layout)) return MXQ_E_SHAPE;
+    if (!aligned16(qweight) || !aligned16(rowmeta) || !aligned16(wt16)) return MXQ_E_ALIGN;
+    return mxq_launch_dequant_t_f16(qweight, rowmeta, wt16, N, K, layout == MXQ_LAYOUT_MIXEDC, (hipStream_t)stream);
+}
+
+int mxq_dequant_t_bf16(const void* qweight, const void* rowmeta, void* wt16, int N, int K, int layout, void* stream) {
+    if (!qweight || !rowmeta || !wt16) return MXQ_E_NULL;
+    if (!shape_ok(N, K) || !mxq_layout_is_mixed(layout)) return MXQ_E_SHAPE;
+    if (!aligned16(qweight) || !aligned16(rowmeta) || !aligned16(wt16)) return MXQ_E_ALIGN;
+    return mxq_launch_dequant_t_bf16(qweight, rowmeta, wt16, N, K, layout == MXQ_LAYOUT_MIXEDC, (hipStream_t)stream);
+}
+
 static int linear_check(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K) {
     if (!x || !qweight || !rowmeta || !y) return MXQ_E_NULL;
     if (!shape_ok(N, K) || M <= 0) return MXQ_E_SHAPE;
@@ -540,6 +555,91 @@ int mxq_dense_bf16(const void* x, const void* w16, void* y, int M, int N, int K,
     if (variant < 0 || variant > 2) return MXQ_E_SHAPE;
     if (M == 0) return 0;
     return dense_bf16(x, w16, y, M, N, K, variant, (hipStream_t)stream);
+}
+
+// ---- the input gradient's hoisted schedule and its dispatch (include/mxq_hip.h, enum mxq_grad_input_sched) ----------------
+// dx = dy . W' as the dense product of dy [M, N] with W'^T [K, N]: the transposing dequant (csrc/dequant_t.hip) into the
+// caller's scratch, then the dense kernels with the reduction over N -- which they walk in 64-deep steps, hence N % 64 == 0.
+// No workspace, no atomics: deterministic.
+// Where the forced schedules cross (profiles/grad_input_hoisted_bench.txt, tools/grad_input_bench.py; fp16 / bf16 alike).  The
+// fused kernel sliced in N leads while every 128 x 256 tile still gets four slices or more, S = ceil(CUs / tiles) >= 4, i.e.
+// up to 64 tiles: 4096^2 at 256 / 512 tokens (32 / 64 tiles) 43.0 / 61.1 us against 67.9 / 65.9
+// hoisted, 11008 -> 4096 at 512 tokens 121.8 against 136.4.  With fewer slices per tile it falls behind at once: 4096^2 at 640
+// tokens (80 tiles) 97.5 against 65.7, 11008 -> 4096 at 640 tokens 214.8 against 137.2, and 4096 -> 11008, whose 43 tile columns
+// pass 64 tiles with the second tile row, at 129 / 192 tokens (86 tiles) 91.2 / 109.7 against 76.1 / 77.2.  "auto" stays within
+// 10 % of the faster forced schedule at every measured point (worst: 384 tokens x 11008 -> 4096, 6 slices, 150.0 against 136.2);
+// tests/test_grad_input_hoisted_perf.py holds it within 15 %.
+// One tile row (<= 128 tokens) never hoists: the dense kernels' 256-token tiles are mostly empty there.
+static const int GRAD_INPUT_HOIST_MIN = 129;
+
+static bool grad_input_hoists(int M, int N, int K, size_t scratch_bytes) {
+    if (scratch_bytes < (size_t)N * K * 2 || N % 64 != 0 || M < GRAD_INPUT_HOIST_MIN) return false;
+    const int64_t tiles = (int64_t)((M + 127) / 128) * ((K + 255) / 256);   // csrc/gemm_dx.hip: 128 x 256 tiles of dx
+    return 4 * tiles > mxq_cu_count();
+}
+
+// ws_bytes 0: no workspace; scratch_bytes 0: no scratch
+static int plan_grad_input(int M, int N, int K, size_t ws_bytes, size_t scratch_bytes) {
+    if (grad_input_hoists(M, N, K, scratch_bytes)) return MXQ_GRAD_INPUT_HOISTED;
+    return mxq_gemm_dx_slices(M, N, K, grad_input_slab_bytes(ws_bytes)) > 1 ? MXQ_GRAD_INPUT_SLICED : MXQ_GRAD_INPUT_SINGLE;
+}
+
+static int grad_input_hoisted(bool bf16, const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K, int layout,
+                              void* scratch, size_t scratch_bytes, void* stream) {
+    if (!dy || !qweight || !rowmeta || !dx || !scratch) return MXQ_E_NULL;
+    if (!shape_ok(N, K) || M <= 0 || !mxq_layout_is_mixed(layout) || N % 64 != 0) return MXQ_E_SHAPE;
+    if (scratch_bytes < (size_t)N * K * 2) return MXQ_E_SHAPE;
+    if (!aligned16(dy) || !aligned16(qweight) || !aligned16(rowmeta) || !aligned16(dx) || !aligned16(scratch)) return MXQ_E_ALIGN;
+    const bool compact = layout == MXQ_LAYOUT_MIXEDC;
+    const hipStream_t st = (hipStream_t)stream;
+    if (const int e = bf16 ? mxq_launch_dequant_t_bf16(qweight, rowmeta, scratch, N, K, compact, st)
+                           : mxq_launch_dequant_t_f16(qweight, rowmeta, scratch, N, K, compact, st))
+        return e;
+    // the dense kernels' (tokens, out channels, reduction) = (M, K, N)
+    return bf16 ? dense_bf16(dy, scratch, dx, M, K, N, 0, st) : dense_f16(dy, scratch, dx, M, K, N, 0, st);
+}
+
+int mxq_linear_grad_input_f16_hoisted(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                                      int layout, void* scratch, size_t scratch_bytes, void* stream) {
+    return grad_input_hoisted(false, dy, qweight, rowmeta, dx, M, N, K, layout, scratch, scratch_bytes, stream);
+}
+
+int mxq_linear_grad_input_bf16_hoisted(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                                       int layout, void* scratch, size_t scratch_bytes, void* stream) {
+    return grad_input_hoisted(true, dy, qweight, rowmeta, dx, M, N, K, layout, scratch, scratch_bytes, stream);
+}
+
+int mxq_linear_grad_input_schedule(int M, int N, int K, int layout, size_t workspace_bytes, size_t scratch_bytes) {
+    if (!shape_ok(N, K) || M <= 0 || !mxq_layout_is_mixed(layout)) return MXQ_E_SHAPE;
+    return plan_grad_input(M, N, K, workspace_bytes, scratch_bytes);
+}
+
+int mxq_linear_grad_input_hoist_min_tokens(void) { return GRAD_INPUT_HOIST_MIN; }
+
+// the checks of mxq_linear_grad_input_f16 / _bf16, then the scratch's alignment; without a scratch, those entries themselves
+static int grad_input_auto(bool bf16, const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K, int layout,
+                           void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+    const size_t need = mxq_linear_grad_input_workspace_need(M, N, K, layout);
+    if (const int e = grad_input_check(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, need)) return e;
+    if (scratch && !aligned16(scratch)) return MXQ_E_ALIGN;
+    if (scratch && plan_grad_input(M, N, K, workspace ? workspace_bytes : 0, scratch_bytes) == MXQ_GRAD_INPUT_HOISTED)
+        return grad_input_hoisted(bf16, dy, qweight, rowmeta, dx, M, N, K, layout, scratch, scratch_bytes, stream);
+    return bf16 ? mxq_linear_grad_input_bf16(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, stream)
+                : mxq_linear_grad_input_f16(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, stream);
+}
+
+int mxq_linear_grad_input_f16_auto(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                                   int layout, void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes,
+                                   void* stream) {
+    return grad_input_auto(false, dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, scratch, scratch_bytes,
+                                  stream);
+}
+
+int mxq_linear_grad_input_bf16_auto(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                                    int layout, void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes,
+                                    void* stream) {
+    return grad_input_auto(true, dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, scratch, scratch_bytes,
+                                 stream);
 }
 
 // Where the plan switches, read off profiles/bf16_linear_bench.txt (tools/bf16_linear_bench.py; tests/test_bf16_perf.py holds

@@ -20,6 +20,11 @@ int mxq_launch_dequant_f16(const void* qweight, const void* rowmeta, void* out, 
                            hipStream_t stream);
 int mxq_launch_dequant_bf16(const void* qweight, const void* rowmeta, void* out, int N, int K, int compact,
                             hipStream_t stream);   // the same fp32 s * (q - z), rounded once to bf16
+// dequant_t.hip: the same elements written transposed, out = W'^T as a dense [K, N] matrix (the hoisted input gradient)
+int mxq_launch_dequant_t_f16(const void* qweight, const void* rowmeta, void* out, int N, int K, int compact,
+                             hipStream_t stream);
+int mxq_launch_dequant_t_bf16(const void* qweight, const void* rowmeta, void* out, int N, int K, int compact,
+                              hipStream_t stream);
 int mxq_launch_compact(const void* qweight_exact, void* qweight_compact, int N, int K, hipStream_t stream);
 int mxq_launch_quantize_pack(const void* W, int dtype, const uint8_t* dead, void* qweight, void* rowmeta, int N,
                              int K, hipStream_t stream);

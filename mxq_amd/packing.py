@@ -423,6 +423,29 @@ def dequant_bf16(p: PackedMXQ) -> torch.Tensor:
     return out
 
 
+def _dequant_t(p: PackedMXQ, dtype: torch.dtype) -> torch.Tensor:
+    if not isinstance(p, PackedMXQ):
+        raise ValueError("dequant_t needs a PackedMXQ weight (mixed layout, exact or compact metadata)")
+    _need_gpu(p.qweight)
+    out = torch.empty((p.K, p.N), dtype=dtype, device=p.device)
+    lib = _lib.load()
+    fn, what = (lib.mxq_dequant_t_bf16, "mxq_dequant_t_bf16") if dtype == torch.bfloat16 else (lib.mxq_dequant_t_f16, "mxq_dequant_t_f16")
+    with _on_device(p.device):
+        _lib.check(fn(p.qweight.data_ptr(), p.rowmeta.data_ptr(), out.data_ptr(), p.N, p.K, _layout_code(p), _stream(out)), what)
+    return out
+
+
+def dequant_t(p: PackedMXQ) -> torch.Tensor:
+    """The transposed dense fp16 weight, a contiguous [K, N] tensor bit-identical to ``dequant(p).t().contiguous()``: the
+    operand the dense kernels need for the input gradient (include/mxq_hip.h: mxq_dequant_t_f16)."""
+    return _dequant_t(p, torch.float16)
+
+
+def dequant_t_bf16(p: PackedMXQ) -> torch.Tensor:
+    """``dequant_t`` in bf16: bit-identical to ``dequant_bf16(p).t().contiguous()``."""
+    return _dequant_t(p, torch.bfloat16)
+
+
 DENSE_VARIANTS = {"auto": 0, "dense128": 1, "dense256": 2}   # include/mxq_hip.h: mxq_dense_f16 variants
 
 
@@ -553,7 +576,7 @@ def linear(x: torch.Tensor, p, out: Optional[torch.Tensor] = None, path: str = "
     return out.reshape(*x.shape[:-1], p.N)
 
 
-GRAD_INPUT_PATHS = ("auto", "single", "slices")
+GRAD_INPUT_PATHS = ("auto", "single", "slices", "hoisted")
 
 
 def grad_input_slices(M: int, N: int, K: int) -> int:
@@ -567,13 +590,39 @@ def grad_input_slices(M: int, N: int, K: int) -> int:
     return max(1, min(4, fit))
 
 
+def _grad_input_launch(bf16: bool, args: tuple, M: int, p: PackedMXQ, lay: int, device: torch.device, st: int, path: str) -> int:
+    """The C call behind ``linear_grad_input`` / ``linear_grad_input_bf16`` for one path; returns its code."""
+    lib = _lib.load()
+    kind = "bf16" if bf16 else "f16"
+    ptr = lambda t: (t.data_ptr(), t.numel()) if t is not None else (None, 0)   # noqa: E731
+    if path == "auto":
+        ws = gemm_workspace(device, counters=False, stream=st, need=lib.mxq_linear_grad_input_workspace_need(M, p.N, p.K, lay))
+        hoist = M >= lib.mxq_linear_grad_input_hoist_min_tokens() and p.N % 64 == 0
+        scratch = hoist_scratch(device, lib.mxq_hoist_scratch_bytes(p.N, p.K)) if hoist else None
+        return getattr(lib, f"mxq_linear_grad_input_{kind}_auto")(*args, *ptr(ws), *ptr(scratch), st)
+    if path == "hoisted":
+        if p.N % 64 != 0:
+            raise ValueError(f"the hoisted input gradient needs out_features % 64 == 0, got {p.N}")
+        scratch = hoist_scratch(device, lib.mxq_hoist_scratch_bytes(p.N, p.K))
+        return getattr(lib, f"mxq_linear_grad_input_{kind}_hoisted")(*args, *ptr(scratch), st)
+    S = 1 if path == "single" else grad_input_slices(M, p.N, p.K)
+    if path == "slices" and S < 2:
+        raise ValueError(f"the slices of {M} tokens x {p.K} columns do not fit the workspace")
+    ws = gemm_workspace(device, counters=False, stream=st) if S > 1 else None
+    return getattr(lib, f"mxq_linear_grad_input_{kind}_sliced")(*args, S, *ptr(ws), st)
+
+
 def linear_grad_input(dy: torch.Tensor, p: PackedMXQ, out: Optional[torch.Tensor] = None, path: str = "auto") -> torch.Tensor:
     """dx = dy @ W for dy [..., N] fp16 -> [..., K] fp16 (fp32 accumulation), W the dequantised weight of a PackedMXQ
     (exact or compact metadata): the input gradient of ``linear``, computed by the fused dequant kernel without
     materialising W (include/mxq_hip.h: mxq_linear_grad_input_f16).
 
-    path: "auto" (the library's schedule, with a workspace sized by mxq_linear_grad_input_workspace_need), "single" (one
-    launch of whole tiles, no workspace), "slices" (the N reduction split into ``grad_input_slices`` slices: tests)."""
+    path: "auto" (the library's dispatch, mxq_linear_grad_input_f16_auto: a workspace sized by
+    mxq_linear_grad_input_workspace_need and, from mxq_linear_grad_input_hoist_min_tokens() tokens on, the per-device
+    ``hoist_scratch`` the forward's hoisted mode uses -- stream-ordered, so sharing it is safe), "single" (one launch of whole
+    tiles, no workspace), "slices" (the N reduction split into ``grad_input_slices`` slices: tests), "hoisted" (the transposing
+    dequant into the scratch, then the dense kernels: bit-identical to ``linear_dense(dy, dequant_t(p))``; ValueError where
+    out_features % 64 != 0)."""
     if not isinstance(p, PackedMXQ):
         raise ValueError("linear_grad_input needs a PackedMXQ weight (mixed layout, exact or compact metadata)")
     _need_gpu(dy, p.qweight)
@@ -593,24 +642,11 @@ def linear_grad_input(dy: torch.Tensor, p: PackedMXQ, out: Optional[torch.Tensor
         raise ValueError("out must be a contiguous float16 [tokens, in_features] tensor")
     if M == 0:
         return out.reshape(*dy.shape[:-1], p.K)
-    lib = _lib.load()
     lay = _layout_code(p)
     args = (dy2.data_ptr(), p.qweight.data_ptr(), p.rowmeta.data_ptr(), out.data_ptr(), M, p.N, p.K, lay)
     st = _stream(dy2)
     with _on_device(dy.device):
-        if path == "auto":
-            ws = gemm_workspace(dy2.device, counters=False, stream=st,
-                                need=lib.mxq_linear_grad_input_workspace_need(M, p.N, p.K, lay))
-            rc = lib.mxq_linear_grad_input_f16(*args, ws.data_ptr() if ws is not None else None,
-                                               ws.numel() if ws is not None else 0, st)
-        else:
-            S = 1 if path == "single" else grad_input_slices(M, p.N, p.K)
-            if path == "slices" and S < 2:
-                raise ValueError(f"the slices of {M} tokens x {p.K} columns do not fit the workspace")
-            ws = gemm_workspace(dy2.device, counters=False, stream=st) if S > 1 else None
-            rc = lib.mxq_linear_grad_input_f16_sliced(*args, S, ws.data_ptr() if ws is not None else None,
-                                                      ws.numel() if ws is not None else 0, st)
-        _lib.check(rc, f"linear_grad_input[{path}]")
+        _lib.check(_grad_input_launch(False, args, M, p, lay, dy2.device, st, path), f"linear_grad_input[{path}]")
     return out.reshape(*dy.shape[:-1], p.K)
 
 
@@ -690,24 +726,11 @@ def linear_grad_input_bf16(dy: torch.Tensor, p: PackedMXQ, out: Optional[torch.T
         raise ValueError("out must be a contiguous bfloat16 [tokens, in_features] tensor")
     if M == 0:
         return out.reshape(*dy.shape[:-1], p.K)
-    lib = _lib.load()
     lay = _layout_code(p)
     args = (dy2.data_ptr(), p.qweight.data_ptr(), p.rowmeta.data_ptr(), out.data_ptr(), M, p.N, p.K, lay)
     st = _stream(dy2)
     with _on_device(dy.device):
-        if path == "auto":
-            ws = gemm_workspace(dy2.device, counters=False, stream=st,
-                                need=lib.mxq_linear_grad_input_workspace_need(M, p.N, p.K, lay))
-            rc = lib.mxq_linear_grad_input_bf16(*args, ws.data_ptr() if ws is not None else None,
-                                                ws.numel() if ws is not None else 0, st)
-        else:
-            S = 1 if path == "single" else grad_input_slices(M, p.N, p.K)
-            if path == "slices" and S < 2:
-                raise ValueError(f"the slices of {M} tokens x {p.K} columns do not fit the workspace")
-            ws = gemm_workspace(dy2.device, counters=False, stream=st) if S > 1 else None
-            rc = lib.mxq_linear_grad_input_bf16_sliced(*args, S, ws.data_ptr() if ws is not None else None,
-                                                       ws.numel() if ws is not None else 0, st)
-        _lib.check(rc, f"linear_grad_input_bf16[{path}]")
+        _lib.check(_grad_input_launch(True, args, M, p, lay, dy2.device, st, path), f"linear_grad_input_bf16[{path}]")
     return out.reshape(*dy.shape[:-1], p.K)
 
 

@@ -25,8 +25,8 @@ from . import packing
 
 class _QuantLinearFn(torch.autograd.Function):
     """y = x W^T through the packed weight, differentiable in x alone: the forward is exactly ``packing.linear`` (bf16 x:
-    ``packing.linear_bf16``), the backward dx = dy W runs the fused dequant kernel (packing.linear_grad_input /
-    linear_grad_input_bf16) and returns dx in dy's dtype.  No activation is saved -- dx needs the packed weight only -- and
+    ``packing.linear_bf16``), the backward dx = dy W runs packing.linear_grad_input / linear_grad_input_bf16 ("auto": the
+    fused dequant kernel, or from training token counts the hoisted schedule) and returns dx in dy's dtype.  No activation is saved -- dx needs the packed weight only -- and
     the weight's buffers get no gradient (frozen packed base)."""
 
     @staticmethod
