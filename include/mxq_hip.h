@@ -449,11 +449,17 @@ int mxq_lmhead_argmax_advance_f16(const void* h, const void* norm_w, float eps, 
 
 /* MXAsymQuantizer.forward (utils_quant.py:316-462; 2-D, layerwise=False branch):
  * fake-quantise w[rows, cols] of `dtype` into out (same shape/dtype), bit-identical to
- * the reference in fp32 / bf16 / fp16.  cols % 64 == 0. */
+ * the reference in fp32 / bf16 / fp16.  cols % 64 == 0.
+ * Non-finite weights: every range is taken as torch.max / torch.min take it, which propagate NaN.  One NaN weight
+ * turns its whole 16-column 2-bit group NaN; one NaN in a 4-bit slice (the last 16 columns of every 64) turns the
+ * 4-bit arm of the whole ROW NaN.  A +-inf weight makes the range infinite and does the same to its group / arm
+ * (0 * inf).  Nothing is repaired: a weight that went NaN in training shows as it does in the reference.  NaN
+ * payloads are not part of the promise; NaN-ness is. */
 int mxq_fakequant_fwd(const void* w, void* out, int rows, int cols, int num_bits, int dtype, void* stream);
 
 /* MXAsymQuantizer.backward (utils_quant.py:464-475): grad_in = grad_out where
- * lo < w < hi, else 0.  n elements, n % 8 == 0 (n % 4 for fp32). */
+ * lo < w < hi, else 0.  n elements, n % 8 == 0 (n % 4 for fp32).  A NaN weight lets its gradient pass (ge / le
+ * are false), +-inf weights cut it; a gradient that passes comes back bit for bit (-0.0, NaN and inf included). */
 int mxq_fakequant_bwd(const void* grad_out, const void* w, void* grad_in, int64_t n, float lo, float hi, int dtype,
                       void* stream);
 
@@ -469,7 +475,12 @@ int mxq_fakequant_bwd(const void* grad_out, const void* w, void* grad_in, int64_
  *   (a token row of a 3-D activation, a (batch, head) slab of a 4-D tensor, the whole tensor for
  *   layerwise = True); segment i is ranged iff i % period < live, the others get range 0 (3-D inputs:
  *   the reference slices tokens by a group count taken from the hidden size).  seg_len % 8 == 0
- *   (% 4 for fp32).  range_ws: 8 * n_seg bytes of device scratch (overwritten).
+ *   (% 4 for fp32).  range_ws: 8 * n_seg bytes of device scratch (overwritten), 8-byte aligned.
+ * Non-finite elements, both entries: the ranges are torch's max / min / abs-max, which propagate NaN.  A NaN of either
+ *   sign turns its whole group (group entry) or segment (a token row, a (batch, head) slab, the whole tensor when
+ *   layerwise) NaN, wherever in the segment it lies; so does +-inf (symmetric: s = 0 and inf * 0; asymmetric:
+ *   0 * inf).  Columns beyond the last whole group and segments that are not ranged take range 0 and are not
+ *   affected by a NaN elsewhere.
  * The backward of both is mxq_fakequant_bwd (same straight-through clip, utils_quant.py:88-102). */
 int mxq_actquant_group_fwd(const void* x, void* out, int64_t rows, int cols, int group, int num_bits, int symmetric,
                            int dtype, void* stream);

@@ -27,15 +27,12 @@ namespace {
 
 using namespace mxq_fq;
 
-// torch.max / torch.min propagate NaN; fmaxf / fminf do not
-__device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
-__device__ __forceinline__ float nan_min(float a, float b) { return (b < a || b != b) ? b : a; }
-
 // x[j] <- x[j] / d for the lane's VEC values, where the quotient is rounded to T right afterwards.  An IEEE fp32
 // division is ~10 VALU ops; x * v_rcp_f32(d) is two, and fl32(x * rcp(d)) rounds to the same T value as the correctly
 // rounded quotient unless it lies within a few fp32 ulps of one of T's rounding boundaries (mxq_fq_types.h,
 // boundary_key: the screen of the weight fake-quant kernel).  Any lane of the wave near a boundary (or outside the
-// normal range, or fp32 tensors, whose quotients are not re-rounded) sends the wave through the real division.
+// normal range, or fp32 tensors, whose quotients are not re-rounded) sends the wave through the real division; so does a
+// reciprocal that is no normal number (d > 2^126 in bf16, rcp_usable), whose products would all be 0 and pass the screen.
 template <typename T>
 __device__ __forceinline__ void div_vec(float (&x)[T::VEC], float d) {
     if constexpr (T::HAS_FAST_DIV) {
@@ -47,7 +44,7 @@ __device__ __forceinline__ void div_vec(float (&x)[T::VEC], float d) {
             q[j] = x[j] * r;
             key = min(key, T::boundary_key(q[j]));
         }
-        if (!__any(key < T::KEY_LIMIT)) {
+        if (!__any(key < T::KEY_LIMIT || !rcp_usable(r))) {
 #pragma unroll
             for (int j = 0; j < T::VEC; ++j) x[j] = q[j];
             return;
@@ -68,7 +65,7 @@ __device__ __forceinline__ void sym_apply(const float (&v)[T::VEC], float mx, fl
     const float s = T::rnd(T::rnd(1.0f / T::rnd(mx + 1e-6f)) * qmax);
     const float s2 = T::rnd(s + 1e-6f);
 #pragma unroll
-    for (int j = 0; j < T::VEC; ++j) o[j] = v[j] * s;
+    for (int j = 0; j < T::VEC; ++j) o[j] = T::product(v[j], s);   // -0.0 * s and x * 0 keep their sign (mxq_fq_types.h)
     rnd_vec<T>(o);
 #pragma unroll
     for (int j = 0; j < T::VEC; ++j) o[j] = rintf(o[j]);

@@ -41,7 +41,8 @@ __device__ __forceinline__ void quant_vec(const float (&v)[T::VEC], float alpha,
     }
     // (w - beta) / e must be the correctly rounded fp32 quotient re-rounded to T.  Fast path:
     // multiply by v_rcp_f32(e) and screen; any lane near a rounding boundary (or out of the
-    // normal range) sends the wave through the IEEE divide (~5 % of the iterations).
+    // normal range) sends the wave through the IEEE divide (~5 % of the iterations), and so does
+    // a reciprocal that is no normal number (a bf16 range beyond 2^126: rcp_usable).
     bool slow = !T::HAS_FAST_DIV;
     if constexpr (T::HAS_FAST_DIV) {
         const float r = __builtin_amdgcn_rcpf(e);
@@ -51,7 +52,7 @@ __device__ __forceinline__ void quant_vec(const float (&v)[T::VEC], float alpha,
             xn[j] = xs[j] * r;
             key = min(key, T::boundary_key(xn[j]));
         }
-        slow = __any(key < T::KEY_LIMIT);
+        slow = __any(key < T::KEY_LIMIT || !rcp_usable(r));
     }
     if (slow) {
 #pragma unroll
@@ -114,22 +115,22 @@ __global__ __launch_bounds__(256) void mxq_fakequant_fwd_reg_kernel(const void* 
         T::unpack(raw[i], t);
         float mn = t[0], mx = t[0];
 #pragma unroll
-        for (int j = 1; j < VEC; ++j) { mn = fminf(mn, t[j]); mx = fmaxf(mx, t[j]); }
+        for (int j = 1; j < VEC; ++j) { mn = nan_min(mn, t[j]); mx = nan_max(mx, t[j]); }
 #pragma unroll
         for (int o = 1; o < LPG; o <<= 1) {
-            mn = fminf(mn, __shfl_xor(mn, o, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+            mn = nan_min(mn, __shfl_xor(mn, o, 64));
+            mx = nan_max(mx, __shfl_xor(mx, o, 64));
         }
         gmn[i] = mn;
         gmx[i] = mx;
         const bool in4 = active && e0 < part && is4;
-        mn4 = fminf(mn4, in4 ? mn : INFINITY);
-        mx4 = fmaxf(mx4, in4 ? mx : -INFINITY);
+        mn4 = nan_min(mn4, in4 ? mn : INFINITY);
+        mx4 = nan_max(mx4, in4 ? mx : -INFINITY);
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
-        mn4 = fminf(mn4, __shfl_xor(mn4, o, 64));
-        mx4 = fmaxf(mx4, __shfl_xor(mx4, o, 64));
+        mn4 = nan_min(mn4, __shfl_xor(mn4, o, 64));
+        mx4 = nan_max(mx4, __shfl_xor(mx4, o, 64));
     }
     if constexpr (WPR > 1) {
         __shared__ float part_mn[4], part_mx[4];
@@ -141,8 +142,8 @@ __global__ __launch_bounds__(256) void mxq_fakequant_fwd_reg_kernel(const void* 
         const int w0 = wave / WPR * WPR;
 #pragma unroll
         for (int k = 0; k < WPR; ++k) {
-            mn4 = fminf(mn4, part_mn[w0 + k]);
-            mx4 = fmaxf(mx4, part_mx[w0 + k]);
+            mn4 = nan_min(mn4, part_mn[w0 + k]);
+            mx4 = nan_max(mx4, part_mx[w0 + k]);
         }
     }
     if (!active) return;
@@ -180,12 +181,12 @@ __global__ __launch_bounds__(256) void mxq_fakequant_fwd_kernel(const void* __re
     for (int c = lane / LPG; c < NC; c += 64 / LPG) {
         T::load(w, base + (int64_t)c * 64 + 48 + (lane % LPG) * VEC, v);
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) { mn4 = fminf(mn4, v[j]); mx4 = fmaxf(mx4, v[j]); }
+        for (int j = 0; j < VEC; ++j) { mn4 = nan_min(mn4, v[j]); mx4 = nan_max(mx4, v[j]); }
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
-        mn4 = fminf(mn4, __shfl_xor(mn4, o, 64));
-        mx4 = fmaxf(mx4, __shfl_xor(mx4, o, 64));
+        mn4 = nan_min(mn4, __shfl_xor(mn4, o, 64));
+        mx4 = nan_max(mx4, __shfl_xor(mx4, o, 64));
     }
     const float alpha4 = T::rnd(mx4 - mn4);   // fp32 subtraction, cast on assignment (:369-384)
 
@@ -194,11 +195,11 @@ __global__ __launch_bounds__(256) void mxq_fakequant_fwd_kernel(const void* __re
         T::load(w, base + e0, v);
         float mn = v[0], mx = v[0];
 #pragma unroll
-        for (int j = 1; j < VEC; ++j) { mn = fminf(mn, v[j]); mx = fmaxf(mx, v[j]); }
+        for (int j = 1; j < VEC; ++j) { mn = nan_min(mn, v[j]); mx = nan_max(mx, v[j]); }
 #pragma unroll
         for (int o = 1; o < LPG; o <<= 1) {
-            mn = fminf(mn, __shfl_xor(mn, o, 64));
-            mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+            mn = nan_min(mn, __shfl_xor(mn, o, 64));
+            mx = nan_max(mx, __shfl_xor(mx, o, 64));
         }
         const bool is4 = (e0 & 63) >= 48;
         const float alpha = is4 ? alpha4 : T::rnd(mx - mn);

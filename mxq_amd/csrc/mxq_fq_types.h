@@ -20,10 +20,22 @@ __device__ __forceinline__ void st16_nt(void* p, const uint4 q) {
     __builtin_nontemporal_store(r, (u32x4_nt*)p);
 }
 
+// Range reductions: torch.max / torch.min propagate NaN; fmaxf / fminf (v_max_f32 / v_min_f32) return the other operand.
+// One NaN element therefore turns the whole range NaN, as in the reference, and a NaN already held is kept (neither
+// comparison is true against it).  A compare and a select per step instead of one min / max instruction.
+__device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
+__device__ __forceinline__ float nan_min(float a, float b) { return (b < a || b != b) ? b : a; }
+
+// r = v_rcp_f32(d) stands in for a division by d only while 1 / d is a normal number: the instruction flushes a
+// denormal result to zero, so for d > 2^126 (or d infinite, or NaN) every product x * r would be 0 and the fast-division
+// screens below would pass it.  pack.hip guards its reciprocal the same way.
+__device__ __forceinline__ bool rcp_usable(float r) { return r >= 0x1p-126f; }
+
 struct F32 {
     static constexpr int VEC = 4;
     __device__ static __forceinline__ float rnd(float x) { return x; }
     __device__ static __forceinline__ void rnd2(float&, float&) {}
+    __device__ static __forceinline__ float product(float a, float b) { return a * b; }
     __device__ static __forceinline__ bool near_boundary(float) { return true; }
     __device__ static __forceinline__ uint32_t boundary_key(float) { return 0u; }
     static constexpr uint32_t KEY_LIMIT = 1u;
@@ -57,10 +69,13 @@ struct BF16 {
         a = __uint_as_float(u << 16);
         b = __uint_as_float(u & 0xFFFF0000u);
     }
+    __device__ static __forceinline__ float product(float a, float b) { return a * b; }
     // fast-division screen: fl32(x * rcp(e)) rounds to the same bf16 as the correctly rounded
     // fl32(x / e) unless it lies within a few fp32 ulps of a bf16 rounding boundary
-    // (no range test needed: e = bf16(alpha + 1e-8) is a positive normal number, bf16 has fp32's
-    // exponent range, and for inf / NaN inputs product and quotient agree.)
+    // (no range test on the quotient: bf16 has fp32's exponent range, and for inf / NaN inputs product and quotient
+    // agree.  The DIVISOR needs one: e = bf16(alpha + 1e-8) is positive but reaches fp32's largest values, and beyond 2^126
+    // its reciprocal is a denormal number that v_rcp_f32 flushes to zero -- every product is then 0, whose key passes.
+    // The callers test rcp_usable() next to the key.  fp16 cannot get there: e overflows to inf first.)
     __device__ static __forceinline__ bool near_boundary(float a) {
         return ((__float_as_uint(a) + 0x8004u) & 0xFFF8u) == 0u;   // low 16 bits in [0x7FFC, 0x8003]
     }
@@ -100,6 +115,14 @@ struct F16 {
     __device__ static __forceinline__ void rnd2(float& a, float& b) {
         a = (float)(_Float16)a;
         b = (float)(_Float16)b;
+    }
+    // a * b where the SIGN OF A ZERO product reaches the output (the symmetric quantiser: round(x * s) / (s + 1e-6) is -0.0
+    // for x = -0.0, and for every negative x once an infinite range makes s zero).  hipcc folds the fp16 rounding of a
+    // product into v_fma_mixlo_f16 a, b, +0, and -0 + +0 is +0; the empty asm keeps the product a value of its own.
+    __device__ static __forceinline__ float product(float a, float b) {
+        float p = a * b;
+        asm volatile("" : "+v"(p));
+        return p;
     }
     __device__ static __forceinline__ bool near_boundary(float a) {   // 11 significant bits; no shortcut in the
         const uint32_t u = __float_as_uint(a);                          // fp16-subnormal range; either sign

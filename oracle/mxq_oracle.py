@@ -268,7 +268,7 @@ def fakequant_fwd(w, num_bits=2, dtype="fp32"):
         a2 = r(mx - mn)                                  # :354-362 in the tensor dtype
         alpha[:, :, :N2B] = np.repeat(a2, GROUP, axis=2)
         beta[:, :, :N2B] = np.repeat(mn, GROUP, axis=2)
-        s[:, :, :N2B] = F32(2 ** num_bits - 1)           # :366
+        s[:, :, :N2B] = r(F32(2 ** num_bits - 1))        # :366 stored in a tensor of the weight dtype (65535 -> 65536 in bf16)
         w4 = wc[:, :, N2B:].reshape(N, nc * N4B)         # :347,368 fp32 buffer
         a4 = (w4.max(axis=1) - w4.min(axis=1)).astype(F32)   # :369-376 fp32 subtraction
         b4 = w4.min(axis=1)
