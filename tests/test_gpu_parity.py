@@ -92,21 +92,8 @@ def test_arbitrary_params_pack_unpack_dequant_bit_exact(dev, seed, N, K, zscale,
     kernel equals the oracle's fp32 formula rounded once to fp16, overflow to inf included.  Same generator
     as the CPU property test of the host-compiled helpers (tests/test_format_host_emu.py)."""
     from mxq_amd import packing
-    rng = np.random.default_rng(seed)
-    nc, rb = K // 64, N // 16
-    G = 3 * nc
-    p = dict(
-        codes2=rng.integers(0, 4, (N, 48 * nc), dtype=np.uint8), sc2=rng.integers(0, 16, (N, G), dtype=np.uint8),
-        zero2=(rng.standard_normal((N, G)) * zscale).astype(np.float32),
-        qs2=(np.abs(rng.standard_normal((rb, G))) * sscale).astype(np.float32),
-        qz2=(rng.standard_normal((rb, G)) * 6).astype(np.float32),
-        codes4=rng.integers(0, 16, (N, 16 * nc), dtype=np.uint8), sc4=rng.integers(0, 16, (N,), dtype=np.uint8),
-        zero4=(rng.standard_normal((N,)) * zscale).astype(np.float32),
-        qs4=(np.abs(rng.standard_normal((rb,))) * sscale).astype(np.float32),
-        qz4=(rng.standard_normal((rb,)) * 6).astype(np.float32), N=N, K=K)
-    p["zero2"][0, 0] = 0.0
-    p["zero2"][-1, -1] = -0.0
-    p["qs2"][0, 0] = 0.0
+    from tests.ptq_guard import arbitrary_params
+    p = arbitrary_params(seed, N, K, zscale, sscale)
     pk = packing.pack_codes(_to_dev(p, dev), N, K)
     got = packing.unpack(pk)
     for k in KEYS:
