@@ -339,6 +339,36 @@ int mxq_linear_grad_input_bf16_auto(const void* dy, const void* qweight, const v
                                     int layout, void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes,
                                     void* stream);
 
+/* ---- the fp16 input gradient over all four layouts -------------------------------------------------------------------------
+ * The entries above take the mixed layout alone and keep rejecting the others.  These take every layout code
+ * (MXQ_LAYOUT_MIXED, _W2G16, _W4ROW, _MIXEDC; anything else: MXQ_E_SHAPE).  For the two mixed codes each one IS the entry of
+ * the same name without `_layout` (called with the same arguments: same checks, same results).  For MXQ_LAYOUT_W2G16 and
+ * MXQ_LAYOUT_W4ROW the same kernels run behind a dequant front of that layout, and W' is bit-identical to the fp16 weight
+ * mxq_expand_layout writes: fp16(s * (q - z)) formed in fp32.  dx[M, K] = dy[M, N] . W'[N, K], fp32 sums rounded once to fp16
+ * (RNE), deterministic; the schedules (whole tiles / N slices into fp32 slabs beyond the workspace head, which is never
+ * touched, + a combine launch / transposing dequant into the scratch + the dense kernels, N % 64 == 0), the slice rule, the
+ * workspace and scratch sizes and the order of the checks (NULL, then shape / layout / sizes, then 16-byte alignment) are
+ * those of the mixed entries.  Nothing is allocated, nothing synchronises; every entry can be captured in a graph.
+ *
+ * mxq_dequant_t_f16_layout: wt16 = W'^T [K, N], bit-identical to the transpose of mxq_expand_layout's w16.
+ * mxq_linear_grad_input_layout_workspace_need: mxq_linear_grad_input_workspace_need over all four codes (0 when rejected).
+ * mxq_linear_grad_input_layout_schedule: the schedule mxq_linear_grad_input_f16_layout_auto runs (enum
+ * mxq_grad_input_sched), host-only; equal to mxq_linear_grad_input_schedule on the mixed codes.  The rule is the mixed one
+ * with a per-layout slice threshold (csrc/capi.hip GRAD_INPUT_HOIST_SLICES; tools/uniform_grad_input_bench.py measures it). */
+int mxq_dequant_t_f16_layout(const void* qweight, const void* rowmeta, void* wt16, int N, int K, int layout, void* stream);
+size_t mxq_linear_grad_input_layout_workspace_need(int M, int N, int K, int layout);
+int mxq_linear_grad_input_layout_schedule(int M, int N, int K, int layout, size_t workspace_bytes, size_t scratch_bytes);
+int mxq_linear_grad_input_f16_layout(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                                     int layout, void* workspace, size_t workspace_bytes, void* stream);
+int mxq_linear_grad_input_f16_layout_sliced(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N,
+                                            int K, int layout, int slices, void* workspace, size_t workspace_bytes,
+                                            void* stream);
+int mxq_linear_grad_input_f16_layout_hoisted(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N,
+                                             int K, int layout, void* scratch, size_t scratch_bytes, void* stream);
+int mxq_linear_grad_input_f16_layout_auto(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N,
+                                          int K, int layout, void* workspace, size_t workspace_bytes, void* scratch,
+                                          size_t scratch_bytes, void* stream);
+
 /* Uniform-bit-width layouts for the W2A16 / W4A16 / mixed sweep (BASELINE config 5); the mixed
  * layout is layout 0.  1 = W2G16: Quantizer(bits=2, qq_scale_bits=4) on every 16-column group
  * (quantizer.py:61-147), 4.5 bit/weight; 2 = W4ROW: Quantizer(bits=4, qq_scale_bits=4) per row

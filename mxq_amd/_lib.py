@@ -121,6 +121,16 @@ SIGNATURES = {
                                                c_size_t, c_void_p]),
     "mxq_linear_grad_input_bf16_auto": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
                                                 c_size_t, c_void_p]),
+    "mxq_dequant_t_f16_layout": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mxq_linear_grad_input_layout_workspace_need": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "mxq_linear_grad_input_layout_schedule": (c_int, [c_int, c_int, c_int, c_int, c_size_t, c_size_t]),
+    "mxq_linear_grad_input_f16_layout": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "mxq_linear_grad_input_f16_layout_sliced": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                                                                        c_void_p]),
+    "mxq_linear_grad_input_f16_layout_hoisted": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p, c_size_t,
+                                                                         c_void_p]),
+    "mxq_linear_grad_input_f16_layout_auto": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
+                                                      c_size_t, c_void_p]),
     "mxq_gemv_proto_f16": (c_int, [c_void_p] * 9 + [c_int, c_int, c_int, c_int, c_void_p]),
 }
 

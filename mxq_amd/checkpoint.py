@@ -4,7 +4,8 @@ The reference saves the fake-quantised fp16 model with ``model.save_pretrained(a
 (mxq_quant/main.py:96-100), i.e. 16 bit/weight on disk for a 2.5-bit model; this is the packed
 counterpart: one ``model.safetensors`` holding the ordinary ``state_dict``
 (``<name>.qweight`` int32, ``<name>.rowmeta`` float32 [N, 4], ``<name>.fmt`` int32 (version, N, K) with version 1 =
-exact metadata (4.5 bit/weight) or 2 = compact metadata (fp16 zero-points, 3.75 bit/weight),
+exact metadata (4.5 bit/weight), 2 = compact metadata (fp16 zero-points, 3.75 bit/weight), 3 = the uniform W2G16 layout or
+4 = the uniform W4ROW layout (packing.FORMAT_VERSIONS),
 optional ``<name>.bias``; every non-quantised tensor as it is) plus ``mxq_config.json`` naming the
 quantised modules, so that ``load_packed`` can rebuild the module tree before ``load_state_dict``.
 """
@@ -17,6 +18,7 @@ from typing import Dict, Iterable, List, Optional
 import torch
 import torch.nn as nn
 
+from . import packing
 from .quant_linear import QuantLinear
 
 FORMAT = "mxq-v1"
@@ -32,16 +34,18 @@ def _set_submodule(root: nn.Module, dotted: str, new: nn.Module) -> None:
     setattr(parent, parts[-1], new)
 
 
-def pack_model(model: nn.Module, skip: Iterable[str] = ("lm_head",), compact: bool = False) -> List[str]:
+def pack_model(model: nn.Module, skip: Iterable[str] = ("lm_head",), compact: bool = False, layout="mixed") -> List[str]:
     """Replace every ``nn.Linear`` of ``model`` (on the GPU) by ``QuantLinear.from_linear`` -- the
     round-to-nearest MXQ quantisation of its weight -- except modules whose dotted name ends with an
     entry of ``skip`` (the reference quantises decoder layers only, prune.py:347,368).  Returns the
-    names replaced.  For calibrated quantisation use ``mxq_amd.lib.prune.quantize_sequential(pack=True)``."""
+    names replaced.  ``layout``: one layout name for every module, or a callable name -> layout name (the per-layer choice: e.g.
+"w4row" for the few sensitive projections); ``compact`` applies to the modules of the mixed layout.  For calibrated quantisation use ``mxq_amd.lib.prune.quantize_sequential(pack=True)``."""
     skip = tuple(skip)
     names = [n for n, m in model.named_modules() if type(m) is nn.Linear and not any(n == s or n.endswith("." + s) for s in skip)]
     for n in names:
         lin = dict(model.named_modules())[n]
-        _set_submodule(model, n, QuantLinear.from_linear(lin, compact=compact))
+        lay = layout(n) if callable(layout) else layout
+        _set_submodule(model, n, QuantLinear.from_linear(lin, compact=compact and lay == "mixed", layout=lay))
     return names
 
 
@@ -56,10 +60,14 @@ def save_packed(model: nn.Module, directory: str) -> str:
     q = quantized_modules(model)
     if not q:
         raise ValueError("model holds no QuantLinear module: nothing packed to save")
-    # format_version: 1 = every module carries exact metadata (fmt v1); 2 = at least one module is compact (fmt v2)
-    cfg = {"format": FORMAT, "format_version": 2 if any(m.compact for m in q.values()) else 1,
+    # format_version: 1 = every module carries exact metadata (fmt v1); 2 = at least one module is compact (fmt v2);
+    # 3 = at least one module is in a uniform layout (fmt v3 / v4), named by a per-module "layout" entry that the
+    # modules of the mixed layout do not carry
+    uniform = any(m.layout != "mixed" for m in q.values())
+    cfg = {"format": FORMAT, "format_version": 3 if uniform else 2 if any(m.compact for m in q.values()) else 1,
            "quantized": {n: {"in_features": m.in_features, "out_features": m.out_features, "bias": m.bias is not None,
-                             "metadata": "compact" if m.compact else "exact"}
+                             "metadata": "compact" if m.compact else "exact",
+                             **({"layout": m.layout} if m.layout != "mixed" else {})}
                          for n, m in q.items()}}
     sd = {k: v.detach().contiguous().cpu() for k, v in model.state_dict().items()}
     save_file(sd, os.path.join(directory, WEIGHTS_NAME), metadata={"format": FORMAT})
@@ -90,11 +98,12 @@ def load_packed(model: nn.Module, directory: str, device: Optional[torch.device]
             raise ValueError(f"{n}: checkpoint is {spec['out_features']}x{spec['in_features']}, "
                              f"model has {old.out_features}x{old.in_features}")
         _set_submodule(model, n, QuantLinear(spec["in_features"], spec["out_features"], bias=spec["bias"], device=dev,
-                                             compact=spec.get("metadata", "exact") == "compact"))
+                                             compact=spec.get("metadata", "exact") == "compact",
+                                             layout=spec.get("layout", "mixed")))
     sd = load_file(os.path.join(directory, WEIGHTS_NAME))
     for n, spec in cfg["quantized"].items():
         fmt = sd.get(n + ".fmt")
-        ver = 2 if spec.get("metadata", "exact") == "compact" else 1
+        ver = packing.format_version(spec.get("layout", "mixed"), spec.get("metadata", "exact") == "compact")
         if fmt is None or fmt.tolist() != [ver, spec["out_features"], spec["in_features"]]:
             raise ValueError(f"{n}: fmt header {None if fmt is None else fmt.tolist()} does not match mxq_config.json")
     model.load_state_dict(sd, strict=True)

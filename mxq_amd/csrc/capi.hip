@@ -572,15 +572,20 @@ int mxq_dense_bf16(const void* x, const void* w16, void* y, int M, int N, int K,
 // One tile row (<= 128 tokens) never hoists: the dense kernels' 256-token tiles are mostly empty there.
 static const int GRAD_INPUT_HOIST_MIN = 129;
 
-static bool grad_input_hoists(int M, int N, int K, size_t scratch_bytes) {
+// The uniform layouts (mxq_linear_grad_input_f16_layout*) share the tile geometry and hence the rule; what differs is the
+// dequant cost per block (W4ROW: no per-group metadata; W2G16: a fourth LUT group), which moves the crossing only through
+// GRAD_INPUT_HOIST_SLICES: the fused kernel leads while a tile still gets that many slices (indexed by the layout code).
+static const int GRAD_INPUT_HOIST_SLICES[4] = {4, 4, 4, 4};
+
+static bool grad_input_hoists(int M, int N, int K, int layout, size_t scratch_bytes) {
     if (scratch_bytes < (size_t)N * K * 2 || N % 64 != 0 || M < GRAD_INPUT_HOIST_MIN) return false;
     const int64_t tiles = (int64_t)((M + 127) / 128) * ((K + 255) / 256);   // csrc/gemm_dx.hip: 128 x 256 tiles of dx
-    return 4 * tiles > mxq_cu_count();
+    return GRAD_INPUT_HOIST_SLICES[layout] * tiles > mxq_cu_count();
 }
 
 // ws_bytes 0: no workspace; scratch_bytes 0: no scratch
-static int plan_grad_input(int M, int N, int K, size_t ws_bytes, size_t scratch_bytes) {
-    if (grad_input_hoists(M, N, K, scratch_bytes)) return MXQ_GRAD_INPUT_HOISTED;
+static int plan_grad_input(int M, int N, int K, int layout, size_t ws_bytes, size_t scratch_bytes) {
+    if (grad_input_hoists(M, N, K, layout, scratch_bytes)) return MXQ_GRAD_INPUT_HOISTED;
     return mxq_gemm_dx_slices(M, N, K, grad_input_slab_bytes(ws_bytes)) > 1 ? MXQ_GRAD_INPUT_SLICED : MXQ_GRAD_INPUT_SINGLE;
 }
 
@@ -611,7 +616,7 @@ int mxq_linear_grad_input_bf16_hoisted(const void* dy, const void* qweight, cons
 
 int mxq_linear_grad_input_schedule(int M, int N, int K, int layout, size_t workspace_bytes, size_t scratch_bytes) {
     if (!shape_ok(N, K) || M <= 0 || !mxq_layout_is_mixed(layout)) return MXQ_E_SHAPE;
-    return plan_grad_input(M, N, K, workspace_bytes, scratch_bytes);
+    return plan_grad_input(M, N, K, layout, workspace_bytes, scratch_bytes);
 }
 
 int mxq_linear_grad_input_hoist_min_tokens(void) { return GRAD_INPUT_HOIST_MIN; }
@@ -622,7 +627,7 @@ static int grad_input_auto(bool bf16, const void* dy, const void* qweight, const
     const size_t need = mxq_linear_grad_input_workspace_need(M, N, K, layout);
     if (const int e = grad_input_check(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, need)) return e;
     if (scratch && !aligned16(scratch)) return MXQ_E_ALIGN;
-    if (scratch && plan_grad_input(M, N, K, workspace ? workspace_bytes : 0, scratch_bytes) == MXQ_GRAD_INPUT_HOISTED)
+    if (scratch && plan_grad_input(M, N, K, layout, workspace ? workspace_bytes : 0, scratch_bytes) == MXQ_GRAD_INPUT_HOISTED)
         return grad_input_hoisted(bf16, dy, qweight, rowmeta, dx, M, N, K, layout, scratch, scratch_bytes, stream);
     return bf16 ? mxq_linear_grad_input_bf16(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, stream)
                 : mxq_linear_grad_input_f16(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, stream);
@@ -640,6 +645,96 @@ int mxq_linear_grad_input_bf16_auto(const void* dy, const void* qweight, const v
                                     void* stream) {
     return grad_input_auto(true, dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, scratch, scratch_bytes,
                                  stream);
+}
+
+// ---- the fp16 input gradient over all four layouts (include/mxq_hip.h: the *_layout entries) -----------------------------------
+// MXQ_LAYOUT_MIXED / MXQ_LAYOUT_MIXEDC: the entries above, called as they are.  MXQ_LAYOUT_W2G16 / MXQ_LAYOUT_W4ROW: the same
+// kernels behind their own dequant fronts (csrc/gemm_dx.hip, csrc/dequant_t.hip), the same slice rule (mxq_gemm_dx_slices: the
+// tile geometry is the layouts' common one), the same checks in the same order.
+namespace {
+inline bool layout_uniform(int l) { return l == MXQ_LAYOUT_W2G16 || l == MXQ_LAYOUT_W4ROW; }
+int grad_input_uniform_check(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K, int layout,
+                             const void* workspace, size_t workspace_bytes, size_t ws_need) {
+    if (!dy || !qweight || !rowmeta || !dx) return MXQ_E_NULL;
+    if (!shape_ok(N, K) || M <= 0 || !layout_uniform(layout)) return MXQ_E_SHAPE;
+    if (workspace && workspace_bytes < ws_need) return MXQ_E_SHAPE;
+    if (!aligned16(dy) || !aligned16(qweight) || !aligned16(rowmeta) || !aligned16(dx)) return MXQ_E_ALIGN;
+    if (workspace && !aligned16(workspace)) return MXQ_E_ALIGN;
+    return 0;
+}
+}   // namespace
+
+int mxq_dequant_t_f16_layout(const void* qweight, const void* rowmeta, void* wt16, int N, int K, int layout, void* stream) {
+    if (mxq_layout_is_mixed(layout)) return mxq_dequant_t_f16(qweight, rowmeta, wt16, N, K, layout, stream);
+    if (!qweight || !rowmeta || !wt16) return MXQ_E_NULL;
+    if (!shape_ok(N, K) || !layout_uniform(layout)) return MXQ_E_SHAPE;
+    if (!aligned16(qweight) || !aligned16(rowmeta) || !aligned16(wt16)) return MXQ_E_ALIGN;
+    return mxq_launch_dequant_t_f16_layout(qweight, rowmeta, wt16, N, K, layout, (hipStream_t)stream);
+}
+
+size_t mxq_linear_grad_input_layout_workspace_need(int M, int N, int K, int layout) {
+    if (mxq_layout_is_mixed(layout)) return mxq_linear_grad_input_workspace_need(M, N, K, layout);
+    if (!shape_ok(N, K) || M <= 0 || !layout_uniform(layout)) return 0;
+    const int S = mxq_gemm_dx_slices(M, N, K, grad_input_slab_bytes(mxq_gemm8_workspace_bytes()));
+    return S > 1 ? MXQ_WS_HEAD_BYTES + (size_t)S * M * K * 4 : 0;
+}
+
+int mxq_linear_grad_input_f16_layout(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                                     int layout, void* workspace, size_t workspace_bytes, void* stream) {
+    if (mxq_layout_is_mixed(layout))
+        return mxq_linear_grad_input_f16(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, stream);
+    const size_t need = mxq_linear_grad_input_layout_workspace_need(M, N, K, layout);
+    if (const int e = grad_input_uniform_check(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, need)) return e;
+    const int S = workspace ? mxq_gemm_dx_slices(M, N, K, grad_input_slab_bytes(workspace_bytes)) : 1;
+    return mxq_launch_gemm_dx_uniform_f16(dy, qweight, rowmeta, dx, M, N, K, layout,
+                                          S > 1 ? (char*)workspace + MXQ_WS_HEAD_BYTES : nullptr, S, (hipStream_t)stream);
+}
+
+int mxq_linear_grad_input_f16_layout_sliced(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N,
+                                            int K, int layout, int slices, void* workspace, size_t workspace_bytes,
+                                            void* stream) {
+    if (mxq_layout_is_mixed(layout))
+        return mxq_linear_grad_input_f16_sliced(dy, qweight, rowmeta, dx, M, N, K, layout, slices, workspace, workspace_bytes,
+                                                stream);
+    if (slices > 1 && !workspace) return MXQ_E_NULL;
+    const size_t need = slices > 1 && M > 0 && K > 0 ? MXQ_WS_HEAD_BYTES + (size_t)slices * M * K * 4 : 0;
+    if (const int e = grad_input_uniform_check(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, need)) return e;
+    if (slices < 1 || slices > 64) return MXQ_E_SHAPE;
+    return mxq_launch_gemm_dx_uniform_f16(dy, qweight, rowmeta, dx, M, N, K, layout,
+                                          slices > 1 ? (char*)workspace + MXQ_WS_HEAD_BYTES : nullptr, slices,
+                                          (hipStream_t)stream);
+}
+
+int mxq_linear_grad_input_f16_layout_hoisted(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N,
+                                             int K, int layout, void* scratch, size_t scratch_bytes, void* stream) {
+    if (mxq_layout_is_mixed(layout))
+        return mxq_linear_grad_input_f16_hoisted(dy, qweight, rowmeta, dx, M, N, K, layout, scratch, scratch_bytes, stream);
+    if (!dy || !qweight || !rowmeta || !dx || !scratch) return MXQ_E_NULL;
+    if (!shape_ok(N, K) || M <= 0 || !layout_uniform(layout) || N % 64 != 0) return MXQ_E_SHAPE;
+    if (scratch_bytes < (size_t)N * K * 2) return MXQ_E_SHAPE;
+    if (!aligned16(dy) || !aligned16(qweight) || !aligned16(rowmeta) || !aligned16(dx) || !aligned16(scratch)) return MXQ_E_ALIGN;
+    const hipStream_t st = (hipStream_t)stream;
+    if (const int e = mxq_launch_dequant_t_f16_layout(qweight, rowmeta, scratch, N, K, layout, st)) return e;
+    return dense_f16(dy, scratch, dx, M, K, N, 0, st);   // (tokens, out channels, reduction) = (M, K, N)
+}
+
+int mxq_linear_grad_input_layout_schedule(int M, int N, int K, int layout, size_t workspace_bytes, size_t scratch_bytes) {
+    if (!shape_ok(N, K) || M <= 0 || !layout_ok(layout)) return MXQ_E_SHAPE;
+    return plan_grad_input(M, N, K, layout, workspace_bytes, scratch_bytes);
+}
+
+int mxq_linear_grad_input_f16_layout_auto(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N,
+                                          int K, int layout, void* workspace, size_t workspace_bytes, void* scratch,
+                                          size_t scratch_bytes, void* stream) {
+    if (mxq_layout_is_mixed(layout))
+        return mxq_linear_grad_input_f16_auto(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, scratch,
+                                              scratch_bytes, stream);
+    const size_t need = mxq_linear_grad_input_layout_workspace_need(M, N, K, layout);
+    if (const int e = grad_input_uniform_check(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, need)) return e;
+    if (scratch && !aligned16(scratch)) return MXQ_E_ALIGN;
+    if (scratch && plan_grad_input(M, N, K, layout, workspace ? workspace_bytes : 0, scratch_bytes) == MXQ_GRAD_INPUT_HOISTED)
+        return mxq_linear_grad_input_f16_layout_hoisted(dy, qweight, rowmeta, dx, M, N, K, layout, scratch, scratch_bytes, stream);
+    return mxq_linear_grad_input_f16_layout(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, stream);
 }
 
 // Where the plan switches, read off profiles/bf16_linear_bench.txt (tools/bf16_linear_bench.py; tests/test_bf16_perf.py holds

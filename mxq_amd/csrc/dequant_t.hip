@@ -1,5 +1,5 @@
-// Transposing dequant: packed MXQ (mixed layout, exact or compact metadata) -> W'^T as a dense 16-bit [K, N] matrix, every
-// element bit-identical to what the dequant kernels of pack.hip write at [n, k] (mxq_dequant.h: fp32 s * (q - z), one
+// Transposing dequant: packed MXQ (any layout of mxq_format.h; bf16 on the mixed ones only) -> W'^T as a dense 16-bit [K, N] matrix, every
+// element bit-identical to what the dequant / expand kernels of pack.hip write at [n, k] (mxq_dequant.h: fp32 s * (q - z), one
 // rounding to fp16 or bf16).  The first half of the input gradient's hoisted schedule (capi.hip:
 // mxq_linear_grad_input_*_hoisted): the dense kernels compute x . w^T with w contiguous along the reduction, and for
 // dx = dy . W' the reduction runs over N, so they need W'^T.
@@ -37,13 +37,14 @@ __device__ __forceinline__ uint32_t pair16(uint32_t hi, uint32_t lo, uint32_t se
 #endif
 }
 
-template <bool COMPACT, bool BF16>
+template <int LAYOUT, bool BF16>
 __global__ __launch_bounds__(256) void mxq_dequant_t_kernel(const uint32_t* __restrict__ qweight,
                                                             const float4* __restrict__ rowmeta,
                                                             uint16_t* __restrict__ out, int N, int K, int tiles_n) {
     __shared__ uint4 image[64 * DT_ROWS / 8];
     uint32_t* image32 = (uint32_t*)image;
-    typedef MxqMixed<COMPACT> F;
+    typedef MxqMixed<LAYOUT == MXQ_LAYOUT_MIXEDC> F;
+    constexpr int BLK_DW = LAYOUT == MXQ_LAYOUT_W4ROW ? 128 : F::BLK_DW;
     const int NC = K / 64;
     const int tn = blockIdx.x % tiles_n, c = blockIdx.x / tiles_n;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -53,12 +54,21 @@ __global__ __launch_bounds__(256) void mxq_dequant_t_kernel(const uint32_t* __re
         const int b = wave * 2 + i;                       // block of the tile, wave-uniform
         const int rb = tn * (DT_ROWS / 16) + b;
         if (rb * 16 >= N) break;
-        const uint32_t* tile = qweight + ((int64_t)rb * NC + c) * F::BLK_DW;
+        const uint32_t* tile = qweight + ((int64_t)rb * NC + c) * BLK_DW;
         uint32_t o[2][4];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int r = 2 * pair + j;
-            if (qt < 3) {
+            if constexpr (LAYOUT == MXQ_LAYOUT_W2G16) {
+                const uint32_t d = tile[mxq_w2_c2(qt, r)];
+                const float z = __uint_as_float(tile[mxq_w2_z2(qt, r)]);
+                const uint32_t scw = ((const uint16_t*)tile)[mxq_sc_u16(r)];
+                const float qs = __uint_as_float(tile[mxq_qq(qt)]), qz = __uint_as_float(tile[mxq_qq(qt) + 1]);
+                mxq_deq2x8<BF16>(d, h, mxq_scale(qs, qz, (scw >> (4 * qt)) & 15u), z, o[j]);
+            } else if constexpr (LAYOUT == MXQ_LAYOUT_W4ROW) {
+                const float4 m = rowmeta[rb * 16 + r];
+                mxq_deq4x8<BF16>(tile[mxq_w4_c4(qt, h, r)], mxq_scale(m.z, m.w, (uint32_t)m.y), m.x, o[j]);
+            } else if (qt < 3) {
                 const uint32_t d = tile[mxq_c2(qt, r)];
                 const float z = F::z2(tile, qt, r);
                 const uint32_t scw = F::scw(tile, r);
@@ -87,17 +97,13 @@ __global__ __launch_bounds__(256) void mxq_dequant_t_kernel(const uint32_t* __re
     }
 }
 
-template <bool BF16>
-int launch(const void* qweight, const void* rowmeta, void* out, int N, int K, int compact, hipStream_t stream) {
+template <int LAYOUT, bool BF16>
+int launch(const void* qweight, const void* rowmeta, void* out, int N, int K, hipStream_t stream) {
     const int tiles_n = (N + DT_ROWS - 1) / DT_ROWS;
     const int64_t grid = (int64_t)tiles_n * (K / 64);
     if (grid >= ((int64_t)1 << 31)) return (int)hipErrorInvalidValue;
-    if (compact)
-        mxq_dequant_t_kernel<true, BF16><<<(unsigned)grid, 256, 0, stream>>>((const uint32_t*)qweight, (const float4*)rowmeta,
-                                                                             (uint16_t*)out, N, K, tiles_n);
-    else
-        mxq_dequant_t_kernel<false, BF16><<<(unsigned)grid, 256, 0, stream>>>((const uint32_t*)qweight, (const float4*)rowmeta,
-                                                                              (uint16_t*)out, N, K, tiles_n);
+    mxq_dequant_t_kernel<LAYOUT, BF16><<<(unsigned)grid, 256, 0, stream>>>((const uint32_t*)qweight, (const float4*)rowmeta,
+                                                                           (uint16_t*)out, N, K, tiles_n);
     return (int)hipGetLastError();
 }
 
@@ -105,10 +111,21 @@ int launch(const void* qweight, const void* rowmeta, void* out, int N, int K, in
 
 int mxq_launch_dequant_t_f16(const void* qweight, const void* rowmeta, void* out, int N, int K, int compact,
                              hipStream_t stream) {
-    return launch<false>(qweight, rowmeta, out, N, K, compact, stream);
+    return compact ? launch<MXQ_LAYOUT_MIXEDC, false>(qweight, rowmeta, out, N, K, stream)
+                   : launch<MXQ_LAYOUT_MIXED, false>(qweight, rowmeta, out, N, K, stream);
+}
+
+int mxq_launch_dequant_t_f16_layout(const void* qweight, const void* rowmeta, void* out, int N, int K, int layout,
+                                    hipStream_t stream) {
+    switch (layout) {
+        case MXQ_LAYOUT_W2G16: return launch<MXQ_LAYOUT_W2G16, false>(qweight, rowmeta, out, N, K, stream);
+        case MXQ_LAYOUT_W4ROW: return launch<MXQ_LAYOUT_W4ROW, false>(qweight, rowmeta, out, N, K, stream);
+        default: return mxq_launch_dequant_t_f16(qweight, rowmeta, out, N, K, layout == MXQ_LAYOUT_MIXEDC, stream);
+    }
 }
 
 int mxq_launch_dequant_t_bf16(const void* qweight, const void* rowmeta, void* out, int N, int K, int compact,
                               hipStream_t stream) {
-    return launch<true>(qweight, rowmeta, out, N, K, compact, stream);
+    return compact ? launch<MXQ_LAYOUT_MIXEDC, true>(qweight, rowmeta, out, N, K, stream)
+                   : launch<MXQ_LAYOUT_MIXED, true>(qweight, rowmeta, out, N, K, stream);
 }

@@ -1,5 +1,9 @@
 // Input gradient of the quantised Linear: dx[M, K] = dy[M, N] . W'[N, K], W' the bit-exact dequantised weight of a
-// packed MXQ tensor (mixed layout, exact or compact metadata), fp32 accumulation, fp16 result (RNE).  The element type is a
+// packed MXQ tensor (any of the four layouts of mxq_format.h), fp32 accumulation, fp16 result (RNE).  The layout is a template
+// parameter that selects the dequant FRONT of step 2 alone -- mixed (exact / compact metadata), W2G16 (four 2-bit LUT groups
+// per chunk, no rowmeta) or W4ROW (128-dword blocks of 4-bit codes, scale and zero from rowmeta alone; bit-exact with
+// mxq_uniform_expand_kernel) -- everything behind it is shared.  This unit builds the mixed instantiations; gemm_dx_uniform.hip
+// compiles it a second time (MXQ_DX_UNIFORM) for the W2G16 / W4ROW ones, fp16 only.  On the mixed layouts the element type is a
 // template parameter: BF16 = true reads dy as bf16, rounds W' once to bf16 (mxq_dequant_bf16's weight), multiplies with
 // v_mfma_f32_16x16x32_bf16 and rounds dx to bf16 -- the same schedules, the same workspace rule.
 //
@@ -52,15 +56,16 @@ constexpr int DX_Y_BYTES = DX_BM * DX_Y_STRIDE;      // 18432
 
 __device__ __forceinline__ int w_swz(int r) { return 2 * ((r & 3) | ((r >> 1) & 4)); }
 
-template <bool COMPACT, bool SLICED, bool BF16>
+template <int LAYOUT, bool SLICED, bool BF16>
 __global__ __launch_bounds__(DX_THREADS) void mxq_gemm_dx_kernel(const uint16_t* __restrict__ dy,
                                                                      const uint32_t* __restrict__ qweight,
                                                                      const float4* __restrict__ rowmeta,
                                                                      uint16_t* __restrict__ dx, float* __restrict__ slab,
                                                                      int M, int N, int K, int tiles_k, int steps_per) {
-    typedef MxqMixed<COMPACT> F;
-    constexpr int BLK_U4 = F::BLK_DW / 4;
-    constexpr int RAW_U4 = 16 * BLK_U4 + 64;   // 16 blocks, then float4 rowmeta of the step's 64 rows
+    typedef MxqMixed<LAYOUT == MXQ_LAYOUT_MIXEDC> F;
+    constexpr int BLK_U4 = (LAYOUT == MXQ_LAYOUT_W4ROW ? 128 : F::BLK_DW) / 4;
+    // 16 blocks, then float4 rowmeta of the step's 64 rows (W2G16 keeps every parameter inside its blocks: none)
+    constexpr int RAW_U4 = 16 * BLK_U4 + (LAYOUT == MXQ_LAYOUT_W2G16 ? 0 : 64);
     __shared__ __attribute__((aligned(16))) uint8_t smem[DX_W_BYTES + DX_Y_BYTES + RAW_U4 * 16];
     uint8_t* const w_lds = smem;
     uint8_t* const y_lds = smem + DX_W_BYTES;
@@ -136,7 +141,16 @@ __global__ __launch_bounds__(DX_THREADS) void mxq_gemm_dx_kernel(const uint16_t*
             uint32_t o[4] = {0u, 0u, 0u, 0u};
             if (s * (DX_BN / 16) + rbl < NRB) {                   // wave-uniform: rows past N stay zero
                 const uint32_t* t = (const uint32_t*)(raw_lds + b * BLK_U4);
-                if (qt < 3) {
+                if constexpr (LAYOUT == MXQ_LAYOUT_W2G16) {           // four 2-bit groups: the quarter IS the group
+                    const uint32_t d = t[mxq_w2_c2(qt, r)];
+                    const float z = __uint_as_float(t[mxq_w2_z2(qt, r)]);
+                    const uint32_t scw = ((const uint16_t*)t)[mxq_sc_u16(r)];
+                    const float qs = __uint_as_float(t[mxq_qq(qt)]), qz = __uint_as_float(t[mxq_qq(qt) + 1]);
+                    mxq_deq2x8<BF16>(d, h, mxq_scale(qs, qz, (scw >> (4 * qt)) & 15u), z, o);
+                } else if constexpr (LAYOUT == MXQ_LAYOUT_W4ROW) {    // 4-bit codes, the row's one scale / zero
+                    const float4 rm = ((const float4*)(raw_lds + 16 * BLK_U4))[nl];
+                    mxq_deq4x8<BF16>(t[mxq_w4_c4(qt, h, r)], mxq_scale(rm.z, rm.w, (uint32_t)rm.y), rm.x, o);
+                } else if (qt < 3) {
                     const uint32_t d = t[mxq_c2(qt, r)];
                     const float z = F::z2(t, qt, r);
                     const uint32_t scw = F::scw(t, r);
@@ -215,19 +229,19 @@ __global__ __launch_bounds__(256) void mxq_gemm_dx_combine_kernel(const float4* 
     dx[i] = make_uint2(mxq_pack16<BF16>(a.x, a.y), mxq_pack16<BF16>(a.z, a.w));
 }
 
-template <bool COMPACT, bool BF16>
+template <int LAYOUT, bool BF16>
 int launch(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K, void* slab, int S,
            hipStream_t stream) {
     const int tiles_k = (K + DX_BK - 1) / DX_BK, tiles = ((M + DX_BM - 1) / DX_BM) * tiles_k;
     const int steps = (N + DX_BN - 1) / DX_BN;
     if (S <= 1) {
-        mxq_gemm_dx_kernel<COMPACT, false, BF16><<<dim3(tiles), DX_THREADS, 0, stream>>>(
+        mxq_gemm_dx_kernel<LAYOUT, false, BF16><<<dim3(tiles), DX_THREADS, 0, stream>>>(
             (const uint16_t*)dy, (const uint32_t*)qweight, (const float4*)rowmeta, (uint16_t*)dx, nullptr, M, N, K,
             tiles_k, steps);
         return (int)hipGetLastError();
     }
     const int per = (steps + S - 1) / S;
-    mxq_gemm_dx_kernel<COMPACT, true, BF16><<<dim3(tiles, S), DX_THREADS, 0, stream>>>(
+    mxq_gemm_dx_kernel<LAYOUT, true, BF16><<<dim3(tiles, S), DX_THREADS, 0, stream>>>(
         (const uint16_t*)dy, (const uint32_t*)qweight, (const float4*)rowmeta, nullptr, (float*)slab, M, N, K, tiles_k,
         per);
     const int64_t n4 = (int64_t)M * K / 4;
@@ -238,6 +252,13 @@ int launch(const void* dy, const void* qweight, const void* rowmeta, void* dx, i
 
 }   // namespace
 
+#if defined(MXQ_DX_UNIFORM)
+int mxq_launch_gemm_dx_uniform_f16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                                   int layout, void* slab, int slices, hipStream_t stream) {
+    return layout == MXQ_LAYOUT_W2G16 ? launch<MXQ_LAYOUT_W2G16, false>(dy, qweight, rowmeta, dx, M, N, K, slab, slices, stream)
+                                      : launch<MXQ_LAYOUT_W4ROW, false>(dy, qweight, rowmeta, dx, M, N, K, slab, slices, stream);
+}
+#else
 int mxq_gemm_dx_slices(int M, int N, int K, size_t slab_bytes) {
     const int tiles = ((M + DX_BM - 1) / DX_BM) * ((K + DX_BK - 1) / DX_BK);
     const int steps = (N + DX_BN - 1) / DX_BN;
@@ -253,12 +274,13 @@ int mxq_gemm_dx_slices(int M, int N, int K, size_t slab_bytes) {
 
 int mxq_launch_gemm_dx_f16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
                            int layout, void* slab, int slices, hipStream_t stream) {
-    return layout == MXQ_LAYOUT_MIXEDC ? launch<true, false>(dy, qweight, rowmeta, dx, M, N, K, slab, slices, stream)
-                                       : launch<false, false>(dy, qweight, rowmeta, dx, M, N, K, slab, slices, stream);
+    return layout == MXQ_LAYOUT_MIXEDC ? launch<MXQ_LAYOUT_MIXEDC, false>(dy, qweight, rowmeta, dx, M, N, K, slab, slices, stream)
+                                       : launch<MXQ_LAYOUT_MIXED, false>(dy, qweight, rowmeta, dx, M, N, K, slab, slices, stream);
 }
 
 int mxq_launch_gemm_dx_bf16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
                             int layout, void* slab, int slices, hipStream_t stream) {
-    return layout == MXQ_LAYOUT_MIXEDC ? launch<true, true>(dy, qweight, rowmeta, dx, M, N, K, slab, slices, stream)
-                                       : launch<false, true>(dy, qweight, rowmeta, dx, M, N, K, slab, slices, stream);
+    return layout == MXQ_LAYOUT_MIXEDC ? launch<MXQ_LAYOUT_MIXEDC, true>(dy, qweight, rowmeta, dx, M, N, K, slab, slices, stream)
+                                       : launch<MXQ_LAYOUT_MIXED, true>(dy, qweight, rowmeta, dx, M, N, K, slab, slices, stream);
 }
+#endif   // MXQ_DX_UNIFORM

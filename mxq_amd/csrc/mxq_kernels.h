@@ -25,6 +25,9 @@ int mxq_launch_dequant_t_f16(const void* qweight, const void* rowmeta, void* out
                              hipStream_t stream);
 int mxq_launch_dequant_t_bf16(const void* qweight, const void* rowmeta, void* out, int N, int K, int compact,
                               hipStream_t stream);
+// ... of any layout code (fp16; W2G16 / W4ROW: bit-identical to mxq_launch_uniform_expand's w16, transposed)
+int mxq_launch_dequant_t_f16_layout(const void* qweight, const void* rowmeta, void* out, int N, int K, int layout,
+                                    hipStream_t stream);
 int mxq_launch_compact(const void* qweight_exact, void* qweight_compact, int N, int K, hipStream_t stream);
 int mxq_launch_quantize_pack(const void* W, int dtype, const uint8_t* dead, void* qweight, void* rowmeta, int N,
                              int K, hipStream_t stream);
@@ -217,6 +220,9 @@ int mxq_launch_gemm_dx_f16(const void* dy, const void* qweight, const void* rowm
                            int layout, void* slab, int slices, hipStream_t stream);
 int mxq_launch_gemm_dx_bf16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
                             int layout, void* slab, int slices, hipStream_t stream);   // the same kernel on bf16 dy / W' / dx
+// gemm_dx_uniform.hip: the same kernel behind the dequant front of layout MXQ_LAYOUT_W2G16 or MXQ_LAYOUT_W4ROW (fp16)
+int mxq_launch_gemm_dx_uniform_f16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                                   int layout, void* slab, int slices, hipStream_t stream);
 // linear_bf16.hip: the quantised Linear on bf16 activations (mixed layout, exact or compact metadata); bm = 128 | 32: the
 // token tile; `slices` <= 1: one launch of whole tiles, else `slices` K-slices into fp32 slabs at `slab` (slices * M * N * 4
 // bytes) and a combine launch.  mxq_linear_bf16_slices: the slices that fill the chip with `slab_bytes` of slab (1: none)

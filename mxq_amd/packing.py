@@ -298,11 +298,19 @@ class PackedMXQ:
         return 8.0 * self.nbytes() / (self.N * self.K)
 
 
-def concat_packed(ps) -> PackedMXQ:
+def concat_packed(ps):
     """Stack packed weights along the output dimension (e.g. q | k | v, or gate | up): format v1 is
     row-block-major, so this is a plain concatenation of the block arrays and of the row metadata, and one
-    launch then computes all the stacked Linears of a shared input."""
+    launch then computes all the stacked Linears of a shared input.  PackedUniform weights of one layout and one
+    in_features stack the same way (the same [N/16][K/64] block grid)."""
     ps = list(ps)
+    if ps and all(isinstance(p, PackedUniform) for p in ps):
+        if any(p.K != ps[0].K or p.layout != ps[0].layout for p in ps):
+            raise ValueError("concat_packed needs packed weights with the same in_features and layout")
+        return PackedUniform(torch.cat([p.qweight for p in ps]), torch.cat([p.rowmeta for p in ps]),
+                             sum(p.N for p in ps), ps[0].K, ps[0].layout)
+    if any(not isinstance(p, PackedMXQ) for p in ps):
+        raise ValueError("concat_packed needs packed weights of one kind: all PackedMXQ, or PackedUniform of one layout")
     if not ps or any(p.K != ps[0].K or p.compact != ps[0].compact for p in ps):
         raise ValueError("concat_packed needs packed weights with the same in_features and metadata mode")
     return PackedMXQ(torch.cat([p.qweight for p in ps]), torch.cat([p.rowmeta for p in ps]),
@@ -398,8 +406,10 @@ def unpack(p: PackedMXQ) -> Dict[str, torch.Tensor]:
     return out
 
 
-def dequant(p: PackedMXQ) -> torch.Tensor:
-    """Dense fp16 [N, K] fake-quant weight (bit-identical to the reference's write-back)."""
+def dequant(p) -> torch.Tensor:
+    """Dense fp16 [N, K] fake-quant weight (bit-identical to the reference's write-back); a PackedUniform: ``dequant_uniform``."""
+    if isinstance(p, PackedUniform):
+        return dequant_uniform(p)
     _need_gpu(p.qweight)
     out = torch.empty((p.N, p.K), dtype=torch.float16, device=p.device)
     lib = _lib.load()
@@ -423,21 +433,29 @@ def dequant_bf16(p: PackedMXQ) -> torch.Tensor:
     return out
 
 
-def _dequant_t(p: PackedMXQ, dtype: torch.dtype) -> torch.Tensor:
-    if not isinstance(p, PackedMXQ):
-        raise ValueError("dequant_t needs a PackedMXQ weight (mixed layout, exact or compact metadata)")
+def _dequant_t(p, dtype: torch.dtype) -> torch.Tensor:
+    if isinstance(p, PackedUniform) and dtype == torch.bfloat16:
+        raise ValueError("dequant_t_bf16 needs a PackedMXQ weight: bf16 is not built for uniform layouts")
+    if not isinstance(p, (PackedMXQ, PackedUniform)):
+        raise ValueError("dequant_t needs a PackedMXQ or PackedUniform weight")
     _need_gpu(p.qweight)
     out = torch.empty((p.K, p.N), dtype=dtype, device=p.device)
     lib = _lib.load()
+    if isinstance(p, PackedUniform):
+        with _on_device(p.device):
+            _lib.check(lib.mxq_dequant_t_f16_layout(p.qweight.data_ptr(), p.rowmeta.data_ptr(), out.data_ptr(), p.N, p.K,
+                                                    _layout_code(p), _stream(out)), "mxq_dequant_t_f16_layout")
+        return out
     fn, what = (lib.mxq_dequant_t_bf16, "mxq_dequant_t_bf16") if dtype == torch.bfloat16 else (lib.mxq_dequant_t_f16, "mxq_dequant_t_f16")
     with _on_device(p.device):
         _lib.check(fn(p.qweight.data_ptr(), p.rowmeta.data_ptr(), out.data_ptr(), p.N, p.K, _layout_code(p), _stream(out)), what)
     return out
 
 
-def dequant_t(p: PackedMXQ) -> torch.Tensor:
+def dequant_t(p) -> torch.Tensor:
     """The transposed dense fp16 weight, a contiguous [K, N] tensor bit-identical to ``dequant(p).t().contiguous()``: the
-    operand the dense kernels need for the input gradient (include/mxq_hip.h: mxq_dequant_t_f16)."""
+    operand the dense kernels need for the input gradient (include/mxq_hip.h: mxq_dequant_t_f16; a PackedUniform:
+    mxq_dequant_t_f16_layout, bit-identical to ``expand_uniform(p)[0].t()``)."""
     return _dequant_t(p, torch.float16)
 
 
@@ -590,13 +608,16 @@ def grad_input_slices(M: int, N: int, K: int) -> int:
     return max(1, min(4, fit))
 
 
-def _grad_input_launch(bf16: bool, args: tuple, M: int, p: PackedMXQ, lay: int, device: torch.device, st: int, path: str) -> int:
-    """The C call behind ``linear_grad_input`` / ``linear_grad_input_bf16`` for one path; returns its code."""
+def _grad_input_launch(bf16: bool, args: tuple, M: int, p, lay: int, device: torch.device, st: int, path: str) -> int:
+    """The C call behind ``linear_grad_input`` / ``linear_grad_input_bf16`` for one path; returns its code.  A PackedUniform
+    (fp16 only) goes to the entries of the same names with ``_layout`` (include/mxq_hip.h)."""
     lib = _lib.load()
-    kind = "bf16" if bf16 else "f16"
+    uniform = isinstance(p, PackedUniform)
+    kind = "f16_layout" if uniform else "bf16" if bf16 else "f16"
+    ws_need = lib.mxq_linear_grad_input_layout_workspace_need if uniform else lib.mxq_linear_grad_input_workspace_need
     ptr = lambda t: (t.data_ptr(), t.numel()) if t is not None else (None, 0)   # noqa: E731
     if path == "auto":
-        ws = gemm_workspace(device, counters=False, stream=st, need=lib.mxq_linear_grad_input_workspace_need(M, p.N, p.K, lay))
+        ws = gemm_workspace(device, counters=False, stream=st, need=ws_need(M, p.N, p.K, lay))
         hoist = M >= lib.mxq_linear_grad_input_hoist_min_tokens() and p.N % 64 == 0
         scratch = hoist_scratch(device, lib.mxq_hoist_scratch_bytes(p.N, p.K)) if hoist else None
         return getattr(lib, f"mxq_linear_grad_input_{kind}_auto")(*args, *ptr(ws), *ptr(scratch), st)
@@ -612,10 +633,11 @@ def _grad_input_launch(bf16: bool, args: tuple, M: int, p: PackedMXQ, lay: int, 
     return getattr(lib, f"mxq_linear_grad_input_{kind}_sliced")(*args, S, *ptr(ws), st)
 
 
-def linear_grad_input(dy: torch.Tensor, p: PackedMXQ, out: Optional[torch.Tensor] = None, path: str = "auto") -> torch.Tensor:
+def linear_grad_input(dy: torch.Tensor, p, out: Optional[torch.Tensor] = None, path: str = "auto") -> torch.Tensor:
     """dx = dy @ W for dy [..., N] fp16 -> [..., K] fp16 (fp32 accumulation), W the dequantised weight of a PackedMXQ
-    (exact or compact metadata): the input gradient of ``linear``, computed by the fused dequant kernel without
-    materialising W (include/mxq_hip.h: mxq_linear_grad_input_f16).
+    (exact or compact metadata) or of a PackedUniform (``expand_uniform(p)[0]``): the input gradient of ``linear``, computed
+    by the fused dequant kernel without materialising W (include/mxq_hip.h: mxq_linear_grad_input_f16; a PackedUniform:
+    mxq_linear_grad_input_f16_layout and its siblings).
 
     path: "auto" (the library's dispatch, mxq_linear_grad_input_f16_auto: a workspace sized by
     mxq_linear_grad_input_workspace_need and, from mxq_linear_grad_input_hoist_min_tokens() tokens on, the per-device
@@ -623,8 +645,8 @@ def linear_grad_input(dy: torch.Tensor, p: PackedMXQ, out: Optional[torch.Tensor
     tiles, no workspace), "slices" (the N reduction split into ``grad_input_slices`` slices: tests), "hoisted" (the transposing
     dequant into the scratch, then the dense kernels: bit-identical to ``linear_dense(dy, dequant_t(p))``; ValueError where
     out_features % 64 != 0)."""
-    if not isinstance(p, PackedMXQ):
-        raise ValueError("linear_grad_input needs a PackedMXQ weight (mixed layout, exact or compact metadata)")
+    if not isinstance(p, (PackedMXQ, PackedUniform)):
+        raise ValueError("linear_grad_input needs a PackedMXQ or PackedUniform weight")
     _need_gpu(dy, p.qweight)
     if dy.dtype != torch.float16:
         raise ValueError(f"gradients must be float16, got {dy.dtype}")
@@ -805,6 +827,26 @@ def linear_staged(act: torch.Tensor, act_sum: torch.Tensor, p: PackedMXQ, residu
 # uniform layouts of the BASELINE config-5 sweep (W2A16 / W4A16 arms next to the mixed layout)
 # ------------------------------------------------------------------------------------------------
 LAYOUTS = {"mixed": 0, "w2g16": 1, "w4row": 2}
+# The ONE table of module / file format versions (QuantLinear's ``fmt[0]``, checkpoint.py): version -> (layout name, compact
+# metadata).  Not the C layout code (include/mxq_hip.h MXQ_LAYOUT_*), where 3 is the mixed layout with compact metadata.
+FORMAT_VERSIONS = {1: ("mixed", False), 2: ("mixed", True), 3: ("w2g16", False), 4: ("w4row", False)}
+
+
+def format_version(layout: str, compact_meta: bool = False) -> int:
+    """The module format version of a layout name (FORMAT_VERSIONS read backwards); ValueError for a pair that has none."""
+    for ver, key in FORMAT_VERSIONS.items():
+        if key == (layout, bool(compact_meta)):
+            return ver
+    if layout in LAYOUTS and compact_meta:
+        raise ValueError(f"compact metadata exists for the mixed layout only, not for {layout!r}")
+    raise ValueError(f"layout must be one of {sorted(LAYOUTS)}, got {layout!r}")
+
+
+def layout_qweight_bytes(N: int, K: int, layout: str, compact_meta: bool = False) -> int:
+    """Bytes of the block array of a [N, K] weight in a layout (mxq_qweight_bytes_layout)."""
+    check_shape(N, K)
+    format_version(layout, compact_meta)
+    return _lib.load().mxq_qweight_bytes_layout(N, K, 3 if compact_meta else LAYOUTS[layout])
 
 
 @dataclass
@@ -815,6 +857,10 @@ class PackedUniform:
     N: int
     K: int
     layout: str
+
+    @property
+    def device(self):
+        return self.qweight.device
 
     def nbytes(self) -> int:
         return self.qweight.numel() * 4 + self.rowmeta.numel() * 4
@@ -864,3 +910,9 @@ def expand_uniform(p: PackedUniform, codes: bool = True):
         _lib.check(lib.mxq_expand_layout(p.qweight.data_ptr(), p.rowmeta.data_ptr(), w16.data_ptr(), *ptrs, N, K,
                                          LAYOUTS[p.layout], _stream(w16)), "mxq_expand_layout")
     return w16, out
+
+
+def dequant_uniform(p: PackedUniform) -> torch.Tensor:
+    """Dense fp16 [N, K] weight of a PackedUniform: ``expand_uniform(p)[0]`` without the code tensors."""
+    _need_gpu(p.qweight)
+    return expand_uniform(p, codes=False)[0]
