@@ -235,14 +235,19 @@ int mxq_dense_f16(const void* x, const void* w16, void* y, int M, int N, int K, 
  * workspace of at least mxq_linear_grad_input_workspace_need(M, N, K, layout) bytes (16-byte aligned, e.g. the GEMM
  * workspace) the N reduction is split into S slices where the tiles alone do not fill the chip: fp32 partial slabs beyond
  * the head (MXQ_WS_HEAD_BYTES; the head itself is never read or written), summed in slice order by a second launch.
- * Run-to-run deterministic.  MXQ_E_NULL for a missing operand; MXQ_E_SHAPE for M <= 0, N % 16, K % 64, another layout or
- * a too small workspace; MXQ_E_ALIGN for a pointer that is not 16-byte aligned.  need is 0 where the schedule is one
- * launch, else MXQ_WS_HEAD_BYTES + S * M * K * 4 <= mxq_gemm_workspace_bytes(); 0 for rejected arguments.  Host-only. */
+ * Run-to-run deterministic.  need is 0 where the schedule is one launch, else MXQ_WS_HEAD_BYTES + S * M * K * 4 <=
+ * mxq_gemm_workspace_bytes(); 0 for rejected arguments.  Host-only.
+ * THE CHECKS of every mxq_linear_grad_input_* entry, fp16 or bf16, any layout set (one function, csrc/capi.hip
+ * grad_input_check), in this order; the first that fails is the code returned: MXQ_E_NULL for a missing operand; MXQ_E_SHAPE
+ * for M <= 0, N % 16, K % 64 or a layout the entry does not take; MXQ_E_SHAPE for a workspace that is given but smaller than
+ * the schedule needs; MXQ_E_ALIGN for an operand, then for a workspace, that is not 16-byte aligned.  THE WORKSPACE RULE of
+ * every entry is the one above: nothing for one launch, else the head and one fp32 [M, K] slab per slice. */
 int mxq_linear_grad_input_f16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
                               int layout, void* workspace, size_t workspace_bytes, void* stream);
 size_t mxq_linear_grad_input_workspace_need(int M, int N, int K, int layout);
-/* ... with an explicit number of N slices (1..64; 1: one launch, no workspace needed; else a workspace of at least
- * MXQ_WS_HEAD_BYTES + slices * M * K * 4 bytes): the schedules by name, for tests and tools. */
+/* ... with an explicit number of N slices (1..64; 1: one launch, no workspace needed; else a workspace that holds them):
+ * the schedules by name, for tests and tools.  Around the checks above: more than one slice without a workspace is
+ * MXQ_E_NULL before any of them, a slice count outside 1..64 MXQ_E_SHAPE after all of them. */
 int mxq_linear_grad_input_f16_sliced(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N,
                                      int K, int layout, int slices, void* workspace, size_t workspace_bytes,
                                      void* stream);
@@ -306,9 +311,9 @@ int mxq_linear_grad_input_bf16_sliced(const void* dy, const void* qweight, const
  * mxq_linear_grad_input_f16_hoisted / _bf16_hoisted: mxq_dequant_t_* into `scratch` (>= mxq_hoist_scratch_bytes(N, K) = 2 N K
  * bytes, 16-byte aligned, overwritten; transient: nothing is cached between calls), then mxq_dense_f16 / mxq_dense_bf16 with
  * x = dy [M, N] and w16 = W'^T [K, N]: dx [M, K], bit-identical to that dense call.  The dense kernels reduce in 64-deep
- * steps, so the schedule exists where N % 64 == 0 (else MXQ_E_SHAPE).  No workspace is read or written; deterministic.
- * Checks in the family's order: MXQ_E_NULL (an operand or the scratch), MXQ_E_SHAPE (M <= 0, N % 64, K % 64, the layout, a
- * scratch of fewer than 2 N K bytes), MXQ_E_ALIGN.
+ * steps, so the schedule exists where N % 64 == 0.  No workspace is read or written; deterministic.  The checks of
+ * mxq_linear_grad_input_f16 with the scratch in the workspace's place: required (MXQ_E_NULL), at least 2 N K bytes, 16-byte
+ * aligned; N % 64 != 0 is MXQ_E_SHAPE with the other shapes.
  *
  * mxq_linear_grad_input_schedule: the ONE rule that names the schedule a call of this shape runs given a workspace of
  * `workspace_bytes` and a scratch of `scratch_bytes` (0: none), or MXQ_E_SHAPE; host-only.  HOISTED where the scratch holds
@@ -347,8 +352,8 @@ int mxq_linear_grad_input_bf16_auto(const void* dy, const void* qweight, const v
  * mxq_expand_layout writes: fp16(s * (q - z)) formed in fp32.  dx[M, K] = dy[M, N] . W'[N, K], fp32 sums rounded once to fp16
  * (RNE), deterministic; the schedules (whole tiles / N slices into fp32 slabs beyond the workspace head, which is never
  * touched, + a combine launch / transposing dequant into the scratch + the dense kernels, N % 64 == 0), the slice rule, the
- * workspace and scratch sizes and the order of the checks (NULL, then shape / layout / sizes, then 16-byte alignment) are
- * those of the mixed entries.  Nothing is allocated, nothing synchronises; every entry can be captured in a graph.
+ * workspace and scratch sizes and the checks are those of the mixed entries (mxq_linear_grad_input_f16: one implementation
+ * serves both).  Nothing is allocated, nothing synchronises; every entry can be captured in a graph.
  *
  * mxq_dequant_t_f16_layout: wt16 = W'^T [K, N], bit-identical to the transpose of mxq_expand_layout's w16.
  * mxq_linear_grad_input_layout_workspace_need: mxq_linear_grad_input_workspace_need over all four codes (0 when rejected).

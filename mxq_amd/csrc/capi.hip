@@ -100,21 +100,6 @@ int mxq_dequant_bf16(const void* qweight, const void* rowmeta, void* w16, int N,
     return mxq_launch_dequant_bf16(qweight, rowmeta, w16, N, K, layout == MXQ_LAYOUT_MIXEDC, (hipStream_t)stream);
 }
 
-// W'^T as a dense [K, N] matrix, element for element the bits of mxq_dequant_f16 / _bf16 (csrc/dequant_t.hip)
-int mxq_dequant_t_f16(const void* qweight, const void* rowmeta, void* wt16, int N, int K, int layout, void* stream) {
-    if (!qweight || !rowmeta || !wt16) return MXQ_E_NULL;
-    if (!shape_ok(N, K) || !mxq_layout_is_mixed(layout)) return MXQ_E_SHAPE;
-    if (!aligned16(qweight) || !aligned16(rowmeta) || !aligned16(wt16)) return MXQ_E_ALIGN;
-    return mxq_launch_dequant_t_f16(qweight, rowmeta, wt16, N, K, layout == MXQ_LAYOUT_MIXEDC, (hipStream_t)stream);
-}
-
-int mxq_dequant_t_bf16(const void* qweight, const void* rowmeta, void* wt16, int N, int K, int layout, void* stream) {
-    if (!qweight || !rowmeta || !wt16) return MXQ_E_NULL;
-    if (!shape_ok(N, K) || !mxq_layout_is_mixed(layout)) return MXQ_E_SHAPE;
-    if (!aligned16(qweight) || !aligned16(rowmeta) || !aligned16(wt16)) return MXQ_E_ALIGN;
-    return mxq_launch_dequant_t_bf16(qweight, rowmeta, wt16, N, K, layout == MXQ_LAYOUT_MIXEDC, (hipStream_t)stream);
-}
-
 static int linear_check(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K) {
     if (!x || !qweight || !rowmeta || !y) return MXQ_E_NULL;
     if (!shape_ok(N, K) || M <= 0) return MXQ_E_SHAPE;
@@ -279,15 +264,16 @@ int mxq_gemm_f16_layout(const void* x, const void* qweight, const void* rowmeta,
     return mxq_launch_gemm8_layout_f16(x, qweight, rowmeta, y, M, N, K, layout, nullptr, 0, (hipStream_t)stream);
 }
 
-// y = x . w16^T on a dense fp16 weight: variant 0 = by shape, 1 = the 256 x 128 kernel (gemm8.hip, dense instantiation),
-// 2 = the 256 x 256 kernel (dense256.hip; MXQ_E_SHAPE when the K-tile count is odd)
-static int dense_f16(const void* x, const void* w16, void* y, int M, int N, int K, int variant, hipStream_t stream) {
+// y = x . w16^T on a dense fp16 / bf16 weight (mxq_dense_f16 / mxq_dense_bf16: the bf16 builds of the same two kernels):
+// variant 0 = by shape, 1 = the 256 x 128 kernel (gemm8.hip / gemm8b.hip, dense instantiation), 2 = the 256 x 256 kernel
+// (dense256.hip / dense256_bf16.hip; MXQ_E_SHAPE when the K-tile count is odd)
+static int dense(bool bf16, const void* x, const void* w16, void* y, int M, int N, int K, int variant, hipStream_t stream) {
     if (variant != 1) {
-        const int e = mxq_launch_dense256_f16(x, w16, y, M, N, K, variant == 2, stream);
+        const int e = (bf16 ? mxq_launch_dense256_bf16 : mxq_launch_dense256_f16)(x, w16, y, M, N, K, variant == 2, stream);
         if (e != MXQ_NOT_MY_SHAPE) return e;
         if (variant == 2) return MXQ_E_SHAPE;
     }
-    return mxq_launch_gemm8_dense_f16(x, w16, y, M, N, K, stream);
+    return (bf16 ? mxq_launch_gemm8b_dense_bf16 : mxq_launch_gemm8_dense_f16)(x, w16, y, M, N, K, stream);
 }
 
 size_t mxq_hoist_scratch_bytes(int N, int K) { return shape_ok(N, K) ? (size_t)N * K * 2 : 0; }
@@ -306,16 +292,24 @@ int mxq_linear_f16_hoisted(const void* x, const void* qweight, const void* rowme
         e = mxq_launch_uniform_expand(qweight, rowmeta, w16_scratch, nullptr, nullptr, nullptr, nullptr, nullptr, N, K,
                                       layout, (hipStream_t)stream);
     if (e) return e;
-    return dense_f16(x, w16_scratch, y, M, N, K, 0, (hipStream_t)stream);
+    return dense(false, x, w16_scratch, y, M, N, K, 0, (hipStream_t)stream);
 }
 
-int mxq_dense_f16(const void* x, const void* w16, void* y, int M, int N, int K, int variant, void* stream) {
+static int dense_checked(bool bf16, const void* x, const void* w16, void* y, int M, int N, int K, int variant, void* stream) {
     if (!x || !w16 || !y) return MXQ_E_NULL;
     if (M < 0 || !shape_ok(N, K)) return MXQ_E_SHAPE;
     if (!aligned16(x) || !aligned16(w16) || !aligned16(y)) return MXQ_E_ALIGN;
     if (variant < 0 || variant > 2) return MXQ_E_SHAPE;
     if (M == 0) return 0;
-    return dense_f16(x, w16, y, M, N, K, variant, (hipStream_t)stream);
+    return dense(bf16, x, w16, y, M, N, K, variant, (hipStream_t)stream);
+}
+
+int mxq_dense_f16(const void* x, const void* w16, void* y, int M, int N, int K, int variant, void* stream) {
+    return dense_checked(false, x, w16, y, M, N, K, variant, stream);
+}
+
+int mxq_dense_bf16(const void* x, const void* w16, void* y, int M, int N, int K, int variant, void* stream) {
+    return dense_checked(true, x, w16, y, M, N, K, variant, stream);
 }
 
 // ---- the quantised Linear: ONE dispatch rule (include/mxq_hip.h, enum mxq_linear_sched) ---------------------------------
@@ -472,92 +466,66 @@ size_t mxq_linear_workspace_need(int M, int N, int K, int layout, int hoisting) 
 
 int mxq_hoist_min_tokens(void) { return HOIST_MIN_TOKENS; }
 
-// input gradient of the quantised Linear (csrc/gemm_dx.hip): arguments checked in the order of the Linear family
-// (NULL, then shapes and the workspace's size, then alignment); `slab_need` is the workspace the schedule needs (0: none)
+// ---- the input gradient of the quantised Linear, dx = dy . W' (include/mxq_hip.h, enum mxq_grad_input_sched) ----------------
+// ONE check, ONE workspace rule, ONE planner and one runner per schedule behind every mxq_linear_grad_input_* entry.  An entry
+// is an element type (fp16 | bf16) and the layout codes it admits: the mixed ones for the _f16 / _bf16 entries, all four for the
+// _f16_layout entries.  Two schedules:
+//   * fused (csrc/gemm_dx.hip): W' dequantised inside the GEMM; one launch of whole tiles, or S slices of the N reduction into
+//     fp32 slabs behind the workspace's head and a combine launch (mxq_gemm_dx_slices: the tile geometry, and hence the slice
+//     rule, is common to the layouts);
+//   * hoisted: the transposing dequant (csrc/dequant_t.hip) into the caller's scratch, then the dense kernels.
 namespace {
+struct GradInputKind {            // what an entry is built for
+    bool bf16;                    // the element type of dy, W' and dx: bf16 or fp16
+    bool (*admits)(int);          // the layout codes it takes; any other is MXQ_E_SHAPE
+};
+const GradInputKind DX_F16 = {false, mxq_layout_is_mixed}, DX_BF16 = {true, mxq_layout_is_mixed}, DX_F16_LAYOUT = {false, layout_ok};
+
+struct GradInputArgs {            // what every entry takes: dy [M, N], the packed W' [N, K], dx [M, K]
+    const void *dy, *qweight, *rowmeta;
+    void* dx;
+    int M, N, K, layout;
+};
+
+// The two maps from (element type, layout) to a launcher: the only places that know which combinations are built.
+// MXQ_E_SHAPE: not built (bf16 on the uniform layouts, which no bf16 entry admits).
+int launch_gemm_dx(bool bf16, const GradInputArgs& a, void* slab, int slices, hipStream_t st) {
+    if (mxq_layout_is_mixed(a.layout))
+        return (bf16 ? mxq_launch_gemm_dx_bf16 : mxq_launch_gemm_dx_f16)(a.dy, a.qweight, a.rowmeta, a.dx, a.M, a.N, a.K, a.layout,
+                                                                       slab, slices, st);
+    if (bf16) return MXQ_E_SHAPE;
+    return mxq_launch_gemm_dx_uniform_f16(a.dy, a.qweight, a.rowmeta, a.dx, a.M, a.N, a.K, a.layout, slab, slices, st);
+}
+int launch_dequant_t(bool bf16, const void* qweight, const void* rowmeta, void* wt16, int N, int K, int layout, hipStream_t st) {
+    if (mxq_layout_is_mixed(layout))
+        return (bf16 ? mxq_launch_dequant_t_bf16 : mxq_launch_dequant_t_f16)(qweight, rowmeta, wt16, N, K,
+                                                                           layout == MXQ_LAYOUT_MIXEDC, st);
+    if (bf16) return MXQ_E_SHAPE;
+    return mxq_launch_dequant_t_f16_layout(qweight, rowmeta, wt16, N, K, layout, st);
+}
+
+// W'^T as a dense [K, N] matrix, element for element the bits of mxq_dequant_f16 / _bf16 / mxq_expand_layout's w16
+int dequant_t(GradInputKind k, const void* qweight, const void* rowmeta, void* wt16, int N, int K, int layout,
+              void* stream) {
+    if (!qweight || !rowmeta || !wt16) return MXQ_E_NULL;
+    if (!shape_ok(N, K) || !k.admits(layout)) return MXQ_E_SHAPE;
+    if (!aligned16(qweight) || !aligned16(rowmeta) || !aligned16(wt16)) return MXQ_E_ALIGN;
+    return launch_dequant_t(k.bf16, qweight, rowmeta, wt16, N, K, layout, (hipStream_t)stream);
+}
+
+// The workspace rule: the head, then one fp32 [M, K] slab per slice; a single launch uses no workspace.
+size_t grad_input_ws_bytes(int slices, int M, int K) {
+    return slices > 1 && M > 0 && K > 0 ? MXQ_WS_HEAD_BYTES + (size_t)slices * M * K * 4 : 0;
+}
 size_t grad_input_slab_bytes(size_t workspace_bytes) {
     return workspace_bytes > MXQ_WS_HEAD_BYTES ? workspace_bytes - MXQ_WS_HEAD_BYTES : 0;
 }
-int grad_input_check(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K, int layout,
-                     const void* workspace, size_t workspace_bytes, size_t ws_need) {
-    if (!dy || !qweight || !rowmeta || !dx) return MXQ_E_NULL;
-    if (!shape_ok(N, K) || M <= 0 || !mxq_layout_is_mixed(layout)) return MXQ_E_SHAPE;
-    if (workspace && workspace_bytes < ws_need) return MXQ_E_SHAPE;
-    if (!aligned16(dy) || !aligned16(qweight) || !aligned16(rowmeta) || !aligned16(dx)) return MXQ_E_ALIGN;
-    if (workspace && !aligned16(workspace)) return MXQ_E_ALIGN;
-    return 0;
-}
-}   // namespace
-
-size_t mxq_linear_grad_input_workspace_need(int M, int N, int K, int layout) {
-    if (!shape_ok(N, K) || M <= 0 || !mxq_layout_is_mixed(layout)) return 0;
-    const int S = mxq_gemm_dx_slices(M, N, K, grad_input_slab_bytes(mxq_gemm8_workspace_bytes()));
-    return S > 1 ? MXQ_WS_HEAD_BYTES + (size_t)S * M * K * 4 : 0;
+// what the planned schedule uses of the GEMM workspace (0: a single launch, or rejected arguments)
+size_t grad_input_ws_need(GradInputKind k, int M, int N, int K, int layout) {
+    if (!shape_ok(N, K) || M <= 0 || !k.admits(layout)) return 0;
+    return grad_input_ws_bytes(mxq_gemm_dx_slices(M, N, K, grad_input_slab_bytes(mxq_gemm8_workspace_bytes())), M, K);
 }
 
-int mxq_linear_grad_input_f16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
-                              int layout, void* workspace, size_t workspace_bytes, void* stream) {
-    const size_t need = mxq_linear_grad_input_workspace_need(M, N, K, layout);
-    if (const int e = grad_input_check(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, need)) return e;
-    const int S = workspace ? mxq_gemm_dx_slices(M, N, K, grad_input_slab_bytes(workspace_bytes)) : 1;
-    return mxq_launch_gemm_dx_f16(dy, qweight, rowmeta, dx, M, N, K, layout,
-                                  S > 1 ? (char*)workspace + MXQ_WS_HEAD_BYTES : nullptr, S, (hipStream_t)stream);
-}
-
-int mxq_linear_grad_input_f16_sliced(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N,
-                                     int K, int layout, int slices, void* workspace, size_t workspace_bytes,
-                                     void* stream) {
-    if (slices > 1 && !workspace) return MXQ_E_NULL;
-    const size_t need = slices > 1 && M > 0 && K > 0 ? MXQ_WS_HEAD_BYTES + (size_t)slices * M * K * 4 : 0;
-    if (const int e = grad_input_check(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, need)) return e;
-    if (slices < 1 || slices > 64) return MXQ_E_SHAPE;
-    return mxq_launch_gemm_dx_f16(dy, qweight, rowmeta, dx, M, N, K, layout,
-                                  slices > 1 ? (char*)workspace + MXQ_WS_HEAD_BYTES : nullptr, slices,
-                                  (hipStream_t)stream);
-}
-
-int mxq_linear_grad_input_bf16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
-                               int layout, void* workspace, size_t workspace_bytes, void* stream) {
-    const size_t need = mxq_linear_grad_input_workspace_need(M, N, K, layout);
-    if (const int e = grad_input_check(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, need)) return e;
-    const int S = workspace ? mxq_gemm_dx_slices(M, N, K, grad_input_slab_bytes(workspace_bytes)) : 1;
-    return mxq_launch_gemm_dx_bf16(dy, qweight, rowmeta, dx, M, N, K, layout,
-                                   S > 1 ? (char*)workspace + MXQ_WS_HEAD_BYTES : nullptr, S, (hipStream_t)stream);
-}
-
-int mxq_linear_grad_input_bf16_sliced(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N,
-                                      int K, int layout, int slices, void* workspace, size_t workspace_bytes,
-                                      void* stream) {
-    if (slices > 1 && !workspace) return MXQ_E_NULL;
-    const size_t need = slices > 1 && M > 0 && K > 0 ? MXQ_WS_HEAD_BYTES + (size_t)slices * M * K * 4 : 0;
-    if (const int e = grad_input_check(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, need)) return e;
-    if (slices < 1 || slices > 64) return MXQ_E_SHAPE;
-    return mxq_launch_gemm_dx_bf16(dy, qweight, rowmeta, dx, M, N, K, layout,
-                                   slices > 1 ? (char*)workspace + MXQ_WS_HEAD_BYTES : nullptr, slices,
-                                   (hipStream_t)stream);
-}
-
-// ---- the quantised Linear on bf16 activations: ONE dispatch rule (include/mxq_hip.h, enum mxq_linear_bf16_sched) ------------
-// y = x . w16^T on a dense bf16 weight: the variants of mxq_dense_f16 on the bf16 builds of the two dense kernels
-static int dense_bf16(const void* x, const void* w16, void* y, int M, int N, int K, int variant, hipStream_t stream) {
-    if (variant != 1) {
-        const int e = mxq_launch_dense256_bf16(x, w16, y, M, N, K, variant == 2, stream);
-        if (e != MXQ_NOT_MY_SHAPE) return e;
-        if (variant == 2) return MXQ_E_SHAPE;
-    }
-    return mxq_launch_gemm8b_dense_bf16(x, w16, y, M, N, K, stream);
-}
-
-int mxq_dense_bf16(const void* x, const void* w16, void* y, int M, int N, int K, int variant, void* stream) {
-    if (!x || !w16 || !y) return MXQ_E_NULL;
-    if (M < 0 || !shape_ok(N, K)) return MXQ_E_SHAPE;
-    if (!aligned16(x) || !aligned16(w16) || !aligned16(y)) return MXQ_E_ALIGN;
-    if (variant < 0 || variant > 2) return MXQ_E_SHAPE;
-    if (M == 0) return 0;
-    return dense_bf16(x, w16, y, M, N, K, variant, (hipStream_t)stream);
-}
-
-// ---- the input gradient's hoisted schedule and its dispatch (include/mxq_hip.h, enum mxq_grad_input_sched) ----------------
 // dx = dy . W' as the dense product of dy [M, N] with W'^T [K, N]: the transposing dequant (csrc/dequant_t.hip) into the
 // caller's scratch, then the dense kernels with the reduction over N -- which they walk in 64-deep steps, hence N % 64 == 0.
 // No workspace, no atomics: deterministic.
@@ -577,166 +545,185 @@ static const int GRAD_INPUT_HOIST_MIN = 129;
 // GRAD_INPUT_HOIST_SLICES: the fused kernel leads while a tile still gets that many slices (indexed by the layout code).
 static const int GRAD_INPUT_HOIST_SLICES[4] = {4, 4, 4, 4};
 
-static bool grad_input_hoists(int M, int N, int K, int layout, size_t scratch_bytes) {
+bool grad_input_hoists(int M, int N, int K, int layout, size_t scratch_bytes) {
     if (scratch_bytes < (size_t)N * K * 2 || N % 64 != 0 || M < GRAD_INPUT_HOIST_MIN) return false;
     const int64_t tiles = (int64_t)((M + 127) / 128) * ((K + 255) / 256);   // csrc/gemm_dx.hip: 128 x 256 tiles of dx
     return GRAD_INPUT_HOIST_SLICES[layout] * tiles > mxq_cu_count();
 }
 
+struct GradInputPlan {
+    int sched;    // enum mxq_grad_input_sched
+    int slices;   // of the fused schedule (1: MXQ_GRAD_INPUT_SINGLE)
+};
+
 // ws_bytes 0: no workspace; scratch_bytes 0: no scratch
-static int plan_grad_input(int M, int N, int K, int layout, size_t ws_bytes, size_t scratch_bytes) {
-    if (grad_input_hoists(M, N, K, layout, scratch_bytes)) return MXQ_GRAD_INPUT_HOISTED;
-    return mxq_gemm_dx_slices(M, N, K, grad_input_slab_bytes(ws_bytes)) > 1 ? MXQ_GRAD_INPUT_SLICED : MXQ_GRAD_INPUT_SINGLE;
+GradInputPlan plan_grad_input(int M, int N, int K, int layout, size_t ws_bytes, size_t scratch_bytes) {
+    if (grad_input_hoists(M, N, K, layout, scratch_bytes)) return {MXQ_GRAD_INPUT_HOISTED, 1};
+    const int S = mxq_gemm_dx_slices(M, N, K, grad_input_slab_bytes(ws_bytes));
+    return {S > 1 ? MXQ_GRAD_INPUT_SLICED : MXQ_GRAD_INPUT_SINGLE, S};
 }
 
-static int grad_input_hoisted(bool bf16, const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K, int layout,
-                              void* scratch, size_t scratch_bytes, void* stream) {
-    if (!dy || !qweight || !rowmeta || !dx || !scratch) return MXQ_E_NULL;
-    if (!shape_ok(N, K) || M <= 0 || !mxq_layout_is_mixed(layout) || N % 64 != 0) return MXQ_E_SHAPE;
-    if (scratch_bytes < (size_t)N * K * 2) return MXQ_E_SHAPE;
-    if (!aligned16(dy) || !aligned16(qweight) || !aligned16(rowmeta) || !aligned16(dx) || !aligned16(scratch)) return MXQ_E_ALIGN;
-    const bool compact = layout == MXQ_LAYOUT_MIXEDC;
-    const hipStream_t st = (hipStream_t)stream;
-    if (const int e = bf16 ? mxq_launch_dequant_t_bf16(qweight, rowmeta, scratch, N, K, compact, st)
-                           : mxq_launch_dequant_t_f16(qweight, rowmeta, scratch, N, K, compact, st))
-        return e;
-    // the dense kernels' (tokens, out channels, reduction) = (M, K, N)
-    return bf16 ? dense_bf16(dy, scratch, dx, M, K, N, 0, st) : dense_f16(dy, scratch, dx, M, K, N, 0, st);
+int grad_input_schedule(GradInputKind k, int M, int N, int K, int layout, size_t workspace_bytes, size_t scratch_bytes) {
+    if (!shape_ok(N, K) || M <= 0 || !k.admits(layout)) return MXQ_E_SHAPE;
+    return plan_grad_input(M, N, K, layout, workspace_bytes, scratch_bytes).sched;
 }
 
-int mxq_linear_grad_input_f16_hoisted(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
-                                      int layout, void* scratch, size_t scratch_bytes, void* stream) {
-    return grad_input_hoisted(false, dy, qweight, rowmeta, dx, M, N, K, layout, scratch, scratch_bytes, stream);
+// The argument check of every entry, in the order of the Linear family: NULL, then the shapes and the layout, then the size of
+// `buf` (the workspace, optional, or the hoisted schedule's scratch) against what the schedule needs, then alignment.
+// n_step: what N must be a multiple of -- 16 (shape_ok) for the fused kernel, 64 for the dense kernels' reduction steps.
+int grad_input_check(GradInputKind k, int n_step, const GradInputArgs& a, const void* buf, size_t buf_bytes, size_t buf_need) {
+    if (!a.dy || !a.qweight || !a.rowmeta || !a.dx) return MXQ_E_NULL;
+    if (!shape_ok(a.N, a.K) || a.M <= 0 || !k.admits(a.layout) || a.N % n_step != 0) return MXQ_E_SHAPE;
+    if (buf && buf_bytes < buf_need) return MXQ_E_SHAPE;
+    if (!aligned16(a.dy) || !aligned16(a.qweight) || !aligned16(a.rowmeta) || !aligned16(a.dx)) return MXQ_E_ALIGN;
+    if (buf && !aligned16(buf)) return MXQ_E_ALIGN;
+    return 0;
 }
 
-int mxq_linear_grad_input_bf16_hoisted(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
-                                       int layout, void* scratch, size_t scratch_bytes, void* stream) {
-    return grad_input_hoisted(true, dy, qweight, rowmeta, dx, M, N, K, layout, scratch, scratch_bytes, stream);
+// the fused schedule: one launch of whole tiles (slices <= 1: no workspace touched), or `slices` slabs + the combine launch
+int run_grad_input_fused(bool bf16, const GradInputArgs& a, void* workspace, int slices, hipStream_t st) {
+    return launch_gemm_dx(bf16, a, slices > 1 ? (char*)workspace + MXQ_WS_HEAD_BYTES : nullptr, slices, st);
+}
+
+// the hoisted schedule
+int run_grad_input_hoisted(bool bf16, const GradInputArgs& a, void* scratch, hipStream_t st) {
+    if (const int e = launch_dequant_t(bf16, a.qweight, a.rowmeta, scratch, a.N, a.K, a.layout, st)) return e;
+    return dense(bf16, a.dy, scratch, a.dx, a.M, a.K, a.N, 0, st);   // (tokens, out channels, reduction) = (M, K, N)
+}
+
+// mxq_linear_grad_input_*_auto, and -- with no scratch, which never hoists -- the plain entries: the planned schedule
+int grad_input_auto(GradInputKind k, const GradInputArgs& a, void* workspace, size_t workspace_bytes, void* scratch,
+                    size_t scratch_bytes, void* stream) {
+    const size_t need = grad_input_ws_need(k, a.M, a.N, a.K, a.layout);
+    if (const int e = grad_input_check(k, 16, a, workspace, workspace_bytes, need)) return e;
+    if (scratch && !aligned16(scratch)) return MXQ_E_ALIGN;
+    const GradInputPlan p = plan_grad_input(a.M, a.N, a.K, a.layout, workspace ? workspace_bytes : 0, scratch ? scratch_bytes : 0);
+    if (p.sched == MXQ_GRAD_INPUT_HOISTED) return run_grad_input_hoisted(k.bf16, a, scratch, (hipStream_t)stream);
+    return run_grad_input_fused(k.bf16, a, workspace, p.slices, (hipStream_t)stream);
+}
+
+// mxq_linear_grad_input_*_sliced: the fused schedule with the caller's slice count, 1 .. 64
+int grad_input_sliced(GradInputKind k, const GradInputArgs& a, int slices, void* workspace, size_t workspace_bytes,
+                      void* stream) {
+    if (slices > 1 && !workspace) return MXQ_E_NULL;
+    if (const int e = grad_input_check(k, 16, a, workspace, workspace_bytes, grad_input_ws_bytes(slices, a.M, a.K))) return e;
+    if (slices < 1 || slices > 64) return MXQ_E_SHAPE;
+    return run_grad_input_fused(k.bf16, a, workspace, slices, (hipStream_t)stream);
+}
+
+// mxq_linear_grad_input_*_hoisted: the hoisted schedule wherever it can run (N % 64 == 0), on a scratch of 2 N K bytes
+int grad_input_hoisted(GradInputKind k, const GradInputArgs& a, void* scratch, size_t scratch_bytes, void* stream) {
+    if (!scratch) return MXQ_E_NULL;
+    if (const int e = grad_input_check(k, 64, a, scratch, scratch_bytes, mxq_hoist_scratch_bytes(a.N, a.K))) return e;
+    return run_grad_input_hoisted(k.bf16, a, scratch, (hipStream_t)stream);
+}
+}   // namespace
+
+int mxq_dequant_t_f16(const void* qweight, const void* rowmeta, void* wt16, int N, int K, int layout, void* stream) {
+    return dequant_t(DX_F16, qweight, rowmeta, wt16, N, K, layout, stream);
+}
+
+int mxq_dequant_t_bf16(const void* qweight, const void* rowmeta, void* wt16, int N, int K, int layout, void* stream) {
+    return dequant_t(DX_BF16, qweight, rowmeta, wt16, N, K, layout, stream);
+}
+
+int mxq_dequant_t_f16_layout(const void* qweight, const void* rowmeta, void* wt16, int N, int K, int layout, void* stream) {
+    return dequant_t(DX_F16_LAYOUT, qweight, rowmeta, wt16, N, K, layout, stream);
+}
+
+size_t mxq_linear_grad_input_workspace_need(int M, int N, int K, int layout) {
+    return grad_input_ws_need(DX_F16, M, N, K, layout);
+}
+
+size_t mxq_linear_grad_input_layout_workspace_need(int M, int N, int K, int layout) {
+    return grad_input_ws_need(DX_F16_LAYOUT, M, N, K, layout);
 }
 
 int mxq_linear_grad_input_schedule(int M, int N, int K, int layout, size_t workspace_bytes, size_t scratch_bytes) {
-    if (!shape_ok(N, K) || M <= 0 || !mxq_layout_is_mixed(layout)) return MXQ_E_SHAPE;
-    return plan_grad_input(M, N, K, layout, workspace_bytes, scratch_bytes);
+    return grad_input_schedule(DX_F16, M, N, K, layout, workspace_bytes, scratch_bytes);
+}
+
+int mxq_linear_grad_input_layout_schedule(int M, int N, int K, int layout, size_t workspace_bytes, size_t scratch_bytes) {
+    return grad_input_schedule(DX_F16_LAYOUT, M, N, K, layout, workspace_bytes, scratch_bytes);
 }
 
 int mxq_linear_grad_input_hoist_min_tokens(void) { return GRAD_INPUT_HOIST_MIN; }
 
-// the checks of mxq_linear_grad_input_f16 / _bf16, then the scratch's alignment; without a scratch, those entries themselves
-static int grad_input_auto(bool bf16, const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K, int layout,
-                           void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes, void* stream) {
-    const size_t need = mxq_linear_grad_input_workspace_need(M, N, K, layout);
-    if (const int e = grad_input_check(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, need)) return e;
-    if (scratch && !aligned16(scratch)) return MXQ_E_ALIGN;
-    if (scratch && plan_grad_input(M, N, K, layout, workspace ? workspace_bytes : 0, scratch_bytes) == MXQ_GRAD_INPUT_HOISTED)
-        return grad_input_hoisted(bf16, dy, qweight, rowmeta, dx, M, N, K, layout, scratch, scratch_bytes, stream);
-    return bf16 ? mxq_linear_grad_input_bf16(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, stream)
-                : mxq_linear_grad_input_f16(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, stream);
+// fp16 on the mixed layouts
+int mxq_linear_grad_input_f16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                              int layout, void* workspace, size_t workspace_bytes, void* stream) {
+    return grad_input_auto(DX_F16, {dy, qweight, rowmeta, dx, M, N, K, layout}, workspace, workspace_bytes, nullptr, 0, stream);
+}
+
+int mxq_linear_grad_input_f16_sliced(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N,
+                                     int K, int layout, int slices, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    return grad_input_sliced(DX_F16, {dy, qweight, rowmeta, dx, M, N, K, layout}, slices, workspace, workspace_bytes, stream);
+}
+
+int mxq_linear_grad_input_f16_hoisted(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                                      int layout, void* scratch, size_t scratch_bytes, void* stream) {
+    return grad_input_hoisted(DX_F16, {dy, qweight, rowmeta, dx, M, N, K, layout}, scratch, scratch_bytes, stream);
 }
 
 int mxq_linear_grad_input_f16_auto(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
                                    int layout, void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes,
                                    void* stream) {
-    return grad_input_auto(false, dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, scratch, scratch_bytes,
-                                  stream);
+    return grad_input_auto(DX_F16, {dy, qweight, rowmeta, dx, M, N, K, layout}, workspace, workspace_bytes, scratch,
+                           scratch_bytes, stream);
+}
+
+// bf16 on the mixed layouts
+int mxq_linear_grad_input_bf16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                               int layout, void* workspace, size_t workspace_bytes, void* stream) {
+    return grad_input_auto(DX_BF16, {dy, qweight, rowmeta, dx, M, N, K, layout}, workspace, workspace_bytes, nullptr, 0, stream);
+}
+
+int mxq_linear_grad_input_bf16_sliced(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N,
+                                      int K, int layout, int slices, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+    return grad_input_sliced(DX_BF16, {dy, qweight, rowmeta, dx, M, N, K, layout}, slices, workspace, workspace_bytes, stream);
+}
+
+int mxq_linear_grad_input_bf16_hoisted(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
+                                       int layout, void* scratch, size_t scratch_bytes, void* stream) {
+    return grad_input_hoisted(DX_BF16, {dy, qweight, rowmeta, dx, M, N, K, layout}, scratch, scratch_bytes, stream);
 }
 
 int mxq_linear_grad_input_bf16_auto(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
                                     int layout, void* workspace, size_t workspace_bytes, void* scratch, size_t scratch_bytes,
                                     void* stream) {
-    return grad_input_auto(true, dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, scratch, scratch_bytes,
-                                 stream);
+    return grad_input_auto(DX_BF16, {dy, qweight, rowmeta, dx, M, N, K, layout}, workspace, workspace_bytes, scratch,
+                           scratch_bytes, stream);
 }
 
-// ---- the fp16 input gradient over all four layouts (include/mxq_hip.h: the *_layout entries) -----------------------------------
-// MXQ_LAYOUT_MIXED / MXQ_LAYOUT_MIXEDC: the entries above, called as they are.  MXQ_LAYOUT_W2G16 / MXQ_LAYOUT_W4ROW: the same
-// kernels behind their own dequant fronts (csrc/gemm_dx.hip, csrc/dequant_t.hip), the same slice rule (mxq_gemm_dx_slices: the
-// tile geometry is the layouts' common one), the same checks in the same order.
-namespace {
-inline bool layout_uniform(int l) { return l == MXQ_LAYOUT_W2G16 || l == MXQ_LAYOUT_W4ROW; }
-int grad_input_uniform_check(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K, int layout,
-                             const void* workspace, size_t workspace_bytes, size_t ws_need) {
-    if (!dy || !qweight || !rowmeta || !dx) return MXQ_E_NULL;
-    if (!shape_ok(N, K) || M <= 0 || !layout_uniform(layout)) return MXQ_E_SHAPE;
-    if (workspace && workspace_bytes < ws_need) return MXQ_E_SHAPE;
-    if (!aligned16(dy) || !aligned16(qweight) || !aligned16(rowmeta) || !aligned16(dx)) return MXQ_E_ALIGN;
-    if (workspace && !aligned16(workspace)) return MXQ_E_ALIGN;
-    return 0;
-}
-}   // namespace
-
-int mxq_dequant_t_f16_layout(const void* qweight, const void* rowmeta, void* wt16, int N, int K, int layout, void* stream) {
-    if (mxq_layout_is_mixed(layout)) return mxq_dequant_t_f16(qweight, rowmeta, wt16, N, K, layout, stream);
-    if (!qweight || !rowmeta || !wt16) return MXQ_E_NULL;
-    if (!shape_ok(N, K) || !layout_uniform(layout)) return MXQ_E_SHAPE;
-    if (!aligned16(qweight) || !aligned16(rowmeta) || !aligned16(wt16)) return MXQ_E_ALIGN;
-    return mxq_launch_dequant_t_f16_layout(qweight, rowmeta, wt16, N, K, layout, (hipStream_t)stream);
-}
-
-size_t mxq_linear_grad_input_layout_workspace_need(int M, int N, int K, int layout) {
-    if (mxq_layout_is_mixed(layout)) return mxq_linear_grad_input_workspace_need(M, N, K, layout);
-    if (!shape_ok(N, K) || M <= 0 || !layout_uniform(layout)) return 0;
-    const int S = mxq_gemm_dx_slices(M, N, K, grad_input_slab_bytes(mxq_gemm8_workspace_bytes()));
-    return S > 1 ? MXQ_WS_HEAD_BYTES + (size_t)S * M * K * 4 : 0;
-}
-
+// fp16 on all four layouts
 int mxq_linear_grad_input_f16_layout(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
                                      int layout, void* workspace, size_t workspace_bytes, void* stream) {
-    if (mxq_layout_is_mixed(layout))
-        return mxq_linear_grad_input_f16(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, stream);
-    const size_t need = mxq_linear_grad_input_layout_workspace_need(M, N, K, layout);
-    if (const int e = grad_input_uniform_check(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, need)) return e;
-    const int S = workspace ? mxq_gemm_dx_slices(M, N, K, grad_input_slab_bytes(workspace_bytes)) : 1;
-    return mxq_launch_gemm_dx_uniform_f16(dy, qweight, rowmeta, dx, M, N, K, layout,
-                                          S > 1 ? (char*)workspace + MXQ_WS_HEAD_BYTES : nullptr, S, (hipStream_t)stream);
+    return grad_input_auto(DX_F16_LAYOUT, {dy, qweight, rowmeta, dx, M, N, K, layout}, workspace, workspace_bytes, nullptr, 0,
+                           stream);
 }
 
 int mxq_linear_grad_input_f16_layout_sliced(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N,
                                             int K, int layout, int slices, void* workspace, size_t workspace_bytes,
                                             void* stream) {
-    if (mxq_layout_is_mixed(layout))
-        return mxq_linear_grad_input_f16_sliced(dy, qweight, rowmeta, dx, M, N, K, layout, slices, workspace, workspace_bytes,
-                                                stream);
-    if (slices > 1 && !workspace) return MXQ_E_NULL;
-    const size_t need = slices > 1 && M > 0 && K > 0 ? MXQ_WS_HEAD_BYTES + (size_t)slices * M * K * 4 : 0;
-    if (const int e = grad_input_uniform_check(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, need)) return e;
-    if (slices < 1 || slices > 64) return MXQ_E_SHAPE;
-    return mxq_launch_gemm_dx_uniform_f16(dy, qweight, rowmeta, dx, M, N, K, layout,
-                                          slices > 1 ? (char*)workspace + MXQ_WS_HEAD_BYTES : nullptr, slices,
-                                          (hipStream_t)stream);
+    return grad_input_sliced(DX_F16_LAYOUT, {dy, qweight, rowmeta, dx, M, N, K, layout}, slices, workspace, workspace_bytes,
+                             stream);
 }
 
 int mxq_linear_grad_input_f16_layout_hoisted(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N,
                                              int K, int layout, void* scratch, size_t scratch_bytes, void* stream) {
-    if (mxq_layout_is_mixed(layout))
-        return mxq_linear_grad_input_f16_hoisted(dy, qweight, rowmeta, dx, M, N, K, layout, scratch, scratch_bytes, stream);
-    if (!dy || !qweight || !rowmeta || !dx || !scratch) return MXQ_E_NULL;
-    if (!shape_ok(N, K) || M <= 0 || !layout_uniform(layout) || N % 64 != 0) return MXQ_E_SHAPE;
-    if (scratch_bytes < (size_t)N * K * 2) return MXQ_E_SHAPE;
-    if (!aligned16(dy) || !aligned16(qweight) || !aligned16(rowmeta) || !aligned16(dx) || !aligned16(scratch)) return MXQ_E_ALIGN;
-    const hipStream_t st = (hipStream_t)stream;
-    if (const int e = mxq_launch_dequant_t_f16_layout(qweight, rowmeta, scratch, N, K, layout, st)) return e;
-    return dense_f16(dy, scratch, dx, M, K, N, 0, st);   // (tokens, out channels, reduction) = (M, K, N)
-}
-
-int mxq_linear_grad_input_layout_schedule(int M, int N, int K, int layout, size_t workspace_bytes, size_t scratch_bytes) {
-    if (!shape_ok(N, K) || M <= 0 || !layout_ok(layout)) return MXQ_E_SHAPE;
-    return plan_grad_input(M, N, K, layout, workspace_bytes, scratch_bytes);
+    return grad_input_hoisted(DX_F16_LAYOUT, {dy, qweight, rowmeta, dx, M, N, K, layout}, scratch, scratch_bytes, stream);
 }
 
 int mxq_linear_grad_input_f16_layout_auto(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N,
                                           int K, int layout, void* workspace, size_t workspace_bytes, void* scratch,
                                           size_t scratch_bytes, void* stream) {
-    if (mxq_layout_is_mixed(layout))
-        return mxq_linear_grad_input_f16_auto(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, scratch,
-                                              scratch_bytes, stream);
-    const size_t need = mxq_linear_grad_input_layout_workspace_need(M, N, K, layout);
-    if (const int e = grad_input_uniform_check(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, need)) return e;
-    if (scratch && !aligned16(scratch)) return MXQ_E_ALIGN;
-    if (scratch && plan_grad_input(M, N, K, layout, workspace ? workspace_bytes : 0, scratch_bytes) == MXQ_GRAD_INPUT_HOISTED)
-        return mxq_linear_grad_input_f16_layout_hoisted(dy, qweight, rowmeta, dx, M, N, K, layout, scratch, scratch_bytes, stream);
-    return mxq_linear_grad_input_f16_layout(dy, qweight, rowmeta, dx, M, N, K, layout, workspace, workspace_bytes, stream);
+    return grad_input_auto(DX_F16_LAYOUT, {dy, qweight, rowmeta, dx, M, N, K, layout}, workspace, workspace_bytes, scratch,
+                           scratch_bytes, stream);
 }
 
+// ---- the quantised Linear on bf16 activations: ONE dispatch rule (include/mxq_hip.h, enum mxq_linear_bf16_sched) ------------
 // Where the plan switches, read off profiles/bf16_linear_bench.txt (tools/bf16_linear_bench.py; tests/test_bf16_perf.py holds
 // "auto" within 15 % of the fastest forced schedule).  Up to BF16_NARROW_MAX tokens the 32-token tile: one tile row holds every
 // token, and sliced it leads the 128-token tile at 32 tokens at all three Llama shapes (28 / 30, 41 / 57, 39 / 44 us); from 48
@@ -770,7 +757,7 @@ static int run_plan_bf16(int sched, const void* x, const void* qweight, const vo
         if (!scratch) return MXQ_E_NULL;
         if (scratch_bytes < (size_t)N * K * 2) return MXQ_E_SHAPE;
         if (const int e = mxq_launch_dequant_bf16(qweight, rowmeta, scratch, N, K, layout == MXQ_LAYOUT_MIXEDC, st)) return e;
-        return dense_bf16(x, scratch, y, M, N, K, 0, st);
+        return dense(true, x, scratch, y, M, N, K, 0, st);
     }
     const int bm = sched == MXQ_BF16_NARROW || sched == MXQ_BF16_NARROW_SLICED ? 32 : 128;
     int S = 1;

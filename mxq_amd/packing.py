@@ -467,55 +467,61 @@ def dequant_t_bf16(p: PackedMXQ) -> torch.Tensor:
 DENSE_VARIANTS = {"auto": 0, "dense128": 1, "dense256": 2}   # include/mxq_hip.h: mxq_dense_f16 variants
 
 
-def linear_dense(x: torch.Tensor, w16: torch.Tensor, out: Optional[torch.Tensor] = None, variant: str = "auto") -> torch.Tensor:
-    """y = x @ w16.T on a dense fp16 [N, K] weight (e.g. ``dequant(p)``): the reference's ``nn.Linear`` on the fake-quant
-    weight (mxq_quant/main.py:85) and the second half of the hoisted mode; fp32 accumulation, fp16 result.
-    variant: "auto", "dense128" (256 x 128-tile kernel), "dense256" (256 x 256-tile kernel; K % 128 == 0)."""
+def _rows(x: torch.Tensor, names: tuple, dtype: torch.dtype, F: int, device: torch.device, out: Optional[torch.Tensor],
+          F_out: int, late_error: Optional[str] = None):
+    """The prologue of the wrappers that map a [..., F] tensor to a [..., F_out] one of the same dtype: checks x (dtype, last
+    dimension, the weight's device), then raises `late_error` (a fault the caller found in its other arguments, reported after
+    x's own), and returns x as contiguous [M, F] rows, `out` allocated or validated as [M, F_out], and M -- with M == 0 the
+    caller launches nothing.  names: x's name, what it holds, the names of F and of F_out in the messages."""
+    name, noun, f_name, out_name = names
+    dt = str(dtype)[6:]
+    if x.dtype != dtype:
+        raise ValueError(f"{noun} must be {dt}, got {x.dtype}")
+    if x.dim() < 1 or x.shape[-1] != F:
+        raise ValueError(f"{f_name} mismatch: {name} has {x.shape[-1] if x.dim() else None}, weight has {F}")
+    if x.device != device:
+        raise ValueError(f"{name} and the packed weight live on different devices")
+    if late_error:
+        raise ValueError(late_error)
+    x2 = x.reshape(-1, F).contiguous()
+    M = x2.shape[0]
+    if out is None:
+        out = torch.empty((M, F_out), dtype=dtype, device=x.device)
+    elif out.shape != (M, F_out) or out.dtype != dtype or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {dt} [tokens, {out_name}] tensor")
+    return x2, out, M
+
+
+def _linear_dense(dtype: torch.dtype, x: torch.Tensor, w16: torch.Tensor, out: Optional[torch.Tensor], variant: str) -> torch.Tensor:
+    short, entry = ("bf16", "mxq_dense_bf16") if dtype == torch.bfloat16 else ("fp16", "mxq_dense_f16")
     _need_gpu(x, w16)
-    if x.dtype != torch.float16 or w16.dtype != torch.float16 or w16.dim() != 2 or x.shape[-1] != w16.shape[1]:
-        raise ValueError("expected fp16 x [..., K] and fp16 w16 [N, K]")
+    if x.dtype != dtype or w16.dtype != dtype or w16.dim() != 2 or x.shape[-1] != w16.shape[1]:
+        raise ValueError(f"expected {short} x [..., K] and {short} w16 [N, K]")
     if not w16.is_contiguous():
         raise ValueError("w16 must be contiguous")
     if variant not in DENSE_VARIANTS:
         raise ValueError(f"unknown variant {variant!r}")
     N, K = w16.shape
     check_shape(N, K)
-    x2 = x.reshape(-1, K).contiguous()
-    M = x2.shape[0]
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.float16, device=x.device)
-    elif out.shape != (M, N) or out.dtype != torch.float16 or not out.is_contiguous():
-        raise ValueError("out must be a contiguous float16 [tokens, out_features] tensor")
+    x2, out, M = _rows(x, ("x", "activations", "K", "out_features"), dtype, K, x.device, out, N)   # (x checked above)
     if M:
         with _on_device(x.device):
-            _lib.check(_lib.load().mxq_dense_f16(x2.data_ptr(), w16.data_ptr(), out.data_ptr(), M, N, K,
-                                                 DENSE_VARIANTS[variant], _stream(x2)), f"mxq_dense_f16[{variant}]")
+            _lib.check(getattr(_lib.load(), entry)(x2.data_ptr(), w16.data_ptr(), out.data_ptr(), M, N, K,
+                                                   DENSE_VARIANTS[variant], _stream(x2)), f"{entry}[{variant}]")
     return out.reshape(*x.shape[:-1], N)
+
+
+def linear_dense(x: torch.Tensor, w16: torch.Tensor, out: Optional[torch.Tensor] = None, variant: str = "auto") -> torch.Tensor:
+    """y = x @ w16.T on a dense fp16 [N, K] weight (e.g. ``dequant(p)``): the reference's ``nn.Linear`` on the fake-quant
+    weight (mxq_quant/main.py:85) and the second half of the hoisted mode; fp32 accumulation, fp16 result.
+    variant: "auto", "dense128" (256 x 128-tile kernel), "dense256" (256 x 256-tile kernel; K % 128 == 0)."""
+    return _linear_dense(torch.float16, x, w16, out, variant)
 
 
 def linear_dense_bf16(x: torch.Tensor, w16: torch.Tensor, out: Optional[torch.Tensor] = None, variant: str = "auto") -> torch.Tensor:
     """``linear_dense`` on bf16 operands: y = x @ w16.T for bf16 x [..., K] and a dense bf16 [N, K] weight (e.g.
     ``dequant_bf16(p)``), fp32 accumulation, bf16 result; the bf16 builds of the same two kernels, the same variants."""
-    _need_gpu(x, w16)
-    if x.dtype != torch.bfloat16 or w16.dtype != torch.bfloat16 or w16.dim() != 2 or x.shape[-1] != w16.shape[1]:
-        raise ValueError("expected bf16 x [..., K] and bf16 w16 [N, K]")
-    if not w16.is_contiguous():
-        raise ValueError("w16 must be contiguous")
-    if variant not in DENSE_VARIANTS:
-        raise ValueError(f"unknown variant {variant!r}")
-    N, K = w16.shape
-    check_shape(N, K)
-    x2 = x.reshape(-1, K).contiguous()
-    M = x2.shape[0]
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
-    elif out.shape != (M, N) or out.dtype != torch.bfloat16 or not out.is_contiguous():
-        raise ValueError("out must be a contiguous bfloat16 [tokens, out_features] tensor")
-    if M:
-        with _on_device(x.device):
-            _lib.check(_lib.load().mxq_dense_bf16(x2.data_ptr(), w16.data_ptr(), out.data_ptr(), M, N, K,
-                                                  DENSE_VARIANTS[variant], _stream(x2)), f"mxq_dense_bf16[{variant}]")
-    return out.reshape(*x.shape[:-1], N)
+    return _linear_dense(torch.bfloat16, x, w16, out, variant)
 
 
 GEMM_PATHS = {"gemm": 0, "fused": 0, "gemm1": 1, "gemm8": 8, "gemm9": 9, "midm": 10, "gemm8h": 12, "gemm8h_split": 13, "gemm8h_slices": 14, "gemm8q_split": 16, "gemm8q_slices": 17, "gemm8n_split": 20, "gemm8n_slices": 21}   # include/mxq_hip.h: enum mxq_gemm_variant
@@ -608,29 +614,60 @@ def grad_input_slices(M: int, N: int, K: int) -> int:
     return max(1, min(4, fit))
 
 
+# the C entry behind each (kind, path) of the input gradient (include/mxq_hip.h); "single" is the sliced entry run with one slice
+_GRAD_INPUT_ENTRIES = {
+    ("f16", "auto"): "mxq_linear_grad_input_f16_auto",
+    ("f16", "single"): "mxq_linear_grad_input_f16_sliced",
+    ("f16", "slices"): "mxq_linear_grad_input_f16_sliced",
+    ("f16", "hoisted"): "mxq_linear_grad_input_f16_hoisted",
+    ("bf16", "auto"): "mxq_linear_grad_input_bf16_auto",
+    ("bf16", "single"): "mxq_linear_grad_input_bf16_sliced",
+    ("bf16", "slices"): "mxq_linear_grad_input_bf16_sliced",
+    ("bf16", "hoisted"): "mxq_linear_grad_input_bf16_hoisted",
+    ("f16_layout", "auto"): "mxq_linear_grad_input_f16_layout_auto",
+    ("f16_layout", "single"): "mxq_linear_grad_input_f16_layout_sliced",
+    ("f16_layout", "slices"): "mxq_linear_grad_input_f16_layout_sliced",
+    ("f16_layout", "hoisted"): "mxq_linear_grad_input_f16_layout_hoisted",
+}
+
+
 def _grad_input_launch(bf16: bool, args: tuple, M: int, p, lay: int, device: torch.device, st: int, path: str) -> int:
     """The C call behind ``linear_grad_input`` / ``linear_grad_input_bf16`` for one path; returns its code.  A PackedUniform
     (fp16 only) goes to the entries of the same names with ``_layout`` (include/mxq_hip.h)."""
     lib = _lib.load()
     uniform = isinstance(p, PackedUniform)
-    kind = "f16_layout" if uniform else "bf16" if bf16 else "f16"
+    entry = getattr(lib, _GRAD_INPUT_ENTRIES["f16_layout" if uniform else "bf16" if bf16 else "f16", path])
     ws_need = lib.mxq_linear_grad_input_layout_workspace_need if uniform else lib.mxq_linear_grad_input_workspace_need
     ptr = lambda t: (t.data_ptr(), t.numel()) if t is not None else (None, 0)   # noqa: E731
     if path == "auto":
         ws = gemm_workspace(device, counters=False, stream=st, need=ws_need(M, p.N, p.K, lay))
         hoist = M >= lib.mxq_linear_grad_input_hoist_min_tokens() and p.N % 64 == 0
         scratch = hoist_scratch(device, lib.mxq_hoist_scratch_bytes(p.N, p.K)) if hoist else None
-        return getattr(lib, f"mxq_linear_grad_input_{kind}_auto")(*args, *ptr(ws), *ptr(scratch), st)
+        return entry(*args, *ptr(ws), *ptr(scratch), st)
     if path == "hoisted":
         if p.N % 64 != 0:
             raise ValueError(f"the hoisted input gradient needs out_features % 64 == 0, got {p.N}")
         scratch = hoist_scratch(device, lib.mxq_hoist_scratch_bytes(p.N, p.K))
-        return getattr(lib, f"mxq_linear_grad_input_{kind}_hoisted")(*args, *ptr(scratch), st)
+        return entry(*args, *ptr(scratch), st)
     S = 1 if path == "single" else grad_input_slices(M, p.N, p.K)
     if path == "slices" and S < 2:
         raise ValueError(f"the slices of {M} tokens x {p.K} columns do not fit the workspace")
     ws = gemm_workspace(device, counters=False, stream=st) if S > 1 else None
-    return getattr(lib, f"mxq_linear_grad_input_{kind}_sliced")(*args, S, *ptr(ws), st)
+    return entry(*args, S, *ptr(ws), st)
+
+
+def _linear_grad_input(dtype: torch.dtype, what: str, dy: torch.Tensor, p, out: Optional[torch.Tensor], path: str) -> torch.Tensor:
+    _need_gpu(dy, p.qweight)
+    dy2, out, M = _rows(dy, ("dy", "gradients", "out_features", "in_features"), dtype, p.N, p.qweight.device, out, p.K,
+                        None if path in GRAD_INPUT_PATHS else f"unknown path {path!r}")
+    if M == 0:
+        return out.reshape(*dy.shape[:-1], p.K)
+    lay = _layout_code(p)
+    args = (dy2.data_ptr(), p.qweight.data_ptr(), p.rowmeta.data_ptr(), out.data_ptr(), M, p.N, p.K, lay)
+    st = _stream(dy2)
+    with _on_device(dy.device):
+        _lib.check(_grad_input_launch(dtype == torch.bfloat16, args, M, p, lay, dy2.device, st, path), f"{what}[{path}]")
+    return out.reshape(*dy.shape[:-1], p.K)
 
 
 def linear_grad_input(dy: torch.Tensor, p, out: Optional[torch.Tensor] = None, path: str = "auto") -> torch.Tensor:
@@ -647,29 +684,7 @@ def linear_grad_input(dy: torch.Tensor, p, out: Optional[torch.Tensor] = None, p
     out_features % 64 != 0)."""
     if not isinstance(p, (PackedMXQ, PackedUniform)):
         raise ValueError("linear_grad_input needs a PackedMXQ or PackedUniform weight")
-    _need_gpu(dy, p.qweight)
-    if dy.dtype != torch.float16:
-        raise ValueError(f"gradients must be float16, got {dy.dtype}")
-    if dy.dim() < 1 or dy.shape[-1] != p.N:
-        raise ValueError(f"out_features mismatch: dy has {dy.shape[-1] if dy.dim() else None}, weight has {p.N}")
-    if dy.device != p.qweight.device:
-        raise ValueError("dy and the packed weight live on different devices")
-    if path not in GRAD_INPUT_PATHS:
-        raise ValueError(f"unknown path {path!r}")
-    dy2 = dy.reshape(-1, p.N).contiguous()
-    M = dy2.shape[0]
-    if out is None:
-        out = torch.empty((M, p.K), dtype=torch.float16, device=dy.device)
-    elif out.shape != (M, p.K) or out.dtype != torch.float16 or not out.is_contiguous():
-        raise ValueError("out must be a contiguous float16 [tokens, in_features] tensor")
-    if M == 0:
-        return out.reshape(*dy.shape[:-1], p.K)
-    lay = _layout_code(p)
-    args = (dy2.data_ptr(), p.qweight.data_ptr(), p.rowmeta.data_ptr(), out.data_ptr(), M, p.N, p.K, lay)
-    st = _stream(dy2)
-    with _on_device(dy.device):
-        _lib.check(_grad_input_launch(False, args, M, p, lay, dy2.device, st, path), f"linear_grad_input[{path}]")
-    return out.reshape(*dy.shape[:-1], p.K)
+    return _linear_grad_input(torch.float16, "linear_grad_input", dy, p, out, path)
 
 
 BF16_PATHS = {"narrow": 1, "narrow_sliced": 2, "wide": 3, "wide_sliced": 4, "hoisted": 5}   # enum mxq_linear_bf16_sched
@@ -686,20 +701,8 @@ def linear_bf16(x: torch.Tensor, p: PackedMXQ, out: Optional[torch.Tensor] = Non
     if not isinstance(p, PackedMXQ):
         raise ValueError("linear_bf16 needs a PackedMXQ weight (mixed layout, exact or compact metadata)")
     _need_gpu(x, p.qweight)
-    if x.dtype != torch.bfloat16:
-        raise ValueError(f"activations must be bfloat16, got {x.dtype}")
-    if x.dim() < 1 or x.shape[-1] != p.K:
-        raise ValueError(f"in_features mismatch: x has {x.shape[-1] if x.dim() else None}, weight has {p.K}")
-    if x.device != p.qweight.device:
-        raise ValueError("x and the packed weight live on different devices")
-    if path != "auto" and path not in BF16_PATHS:
-        raise ValueError(f"unknown path {path!r}")
-    x2 = x.reshape(-1, p.K).contiguous()
-    M = x2.shape[0]
-    if out is None:
-        out = torch.empty((M, p.N), dtype=torch.bfloat16, device=x.device)
-    elif out.shape != (M, p.N) or out.dtype != torch.bfloat16 or not out.is_contiguous():
-        raise ValueError("out must be a contiguous bfloat16 [tokens, out_features] tensor")
+    x2, out, M = _rows(x, ("x", "activations", "in_features", "out_features"), torch.bfloat16, p.K, p.qweight.device, out, p.N,
+                       None if path == "auto" or path in BF16_PATHS else f"unknown path {path!r}")
     if M == 0:
         return out.reshape(*x.shape[:-1], p.N)
     lib = _lib.load()
@@ -731,29 +734,7 @@ def linear_grad_input_bf16(dy: torch.Tensor, p: PackedMXQ, out: Optional[torch.T
     ``linear_bf16`` (include/mxq_hip.h: mxq_linear_grad_input_bf16).  path as in ``linear_grad_input``."""
     if not isinstance(p, PackedMXQ):
         raise ValueError("linear_grad_input_bf16 needs a PackedMXQ weight (mixed layout, exact or compact metadata)")
-    _need_gpu(dy, p.qweight)
-    if dy.dtype != torch.bfloat16:
-        raise ValueError(f"gradients must be bfloat16, got {dy.dtype}")
-    if dy.dim() < 1 or dy.shape[-1] != p.N:
-        raise ValueError(f"out_features mismatch: dy has {dy.shape[-1] if dy.dim() else None}, weight has {p.N}")
-    if dy.device != p.qweight.device:
-        raise ValueError("dy and the packed weight live on different devices")
-    if path not in GRAD_INPUT_PATHS:
-        raise ValueError(f"unknown path {path!r}")
-    dy2 = dy.reshape(-1, p.N).contiguous()
-    M = dy2.shape[0]
-    if out is None:
-        out = torch.empty((M, p.K), dtype=torch.bfloat16, device=dy.device)
-    elif out.shape != (M, p.K) or out.dtype != torch.bfloat16 or not out.is_contiguous():
-        raise ValueError("out must be a contiguous bfloat16 [tokens, in_features] tensor")
-    if M == 0:
-        return out.reshape(*dy.shape[:-1], p.K)
-    lay = _layout_code(p)
-    args = (dy2.data_ptr(), p.qweight.data_ptr(), p.rowmeta.data_ptr(), out.data_ptr(), M, p.N, p.K, lay)
-    st = _stream(dy2)
-    with _on_device(dy.device):
-        _lib.check(_grad_input_launch(True, args, M, p, lay, dy2.device, st, path), f"linear_grad_input_bf16[{path}]")
-    return out.reshape(*dy.shape[:-1], p.K)
+    return _linear_grad_input(torch.bfloat16, "linear_grad_input_bf16", dy, p, out, path)
 
 
 def linear_layout(x: torch.Tensor, p, out: Optional[torch.Tensor] = None, path: str = "gemm") -> torch.Tensor:

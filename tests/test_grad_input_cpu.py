@@ -52,6 +52,16 @@ def test_rejected_arguments(lib):
     assert _gs(lib, slices=2, ws_bytes=HEAD + 2 * 16 * 4096 * 4 - 1) == -1
     assert _gs(lib, slices=2, ws=P + 8, ws_bytes=HEAD + 2 * 16 * 4096 * 4) == -4
     assert _gs(lib, slices=2, layout=2, ws_bytes=1 << 30) == -1
+    # which error wins: slices without a workspace before every other check; the slice range after the alignment
+    for kw in (dict(M=0), dict(N=4088), dict(layout=2), dict(dy=P + 8), dict(slices=65)):
+        assert _gs(lib, ws=None, **{"slices": 2, **kw}) == -2, kw
+    assert _gs(lib, slices=2, ws=None, dy=None, M=0) == -2
+    for slices in (0, 65):
+        assert _gs(lib, slices=slices, ws_bytes=1 << 40, dy=P + 8) == -4
+        assert _gs(lib, slices=slices, ws=P + 8, ws_bytes=1 << 40) == -4
+        assert _gs(lib, slices=slices, ws_bytes=1 << 40, dy=None) == -2
+        assert _gs(lib, slices=slices, ws_bytes=1 << 40, M=0) == -1
+    assert _gs(lib, slices=65, ws_bytes=HEAD + 65 * 16 * 4096 * 4 - 1, dy=P + 8) == -1   # too small a workspace: before the alignment
 
 
 @pytest.mark.parametrize("layout", (0, 3))

@@ -231,3 +231,37 @@ def test_auto_and_autograd_follow_the_rule(dev, lib, side, dtype):
         assert x.grad.shape == x.shape and x.grad.dtype == dtype
         assert torch.equal(bits(x.grad), bits(fn(g, p)))
     packing.workspace_status(dev)
+
+
+# the smallest shapes that reach the three schedules on a 256-CU part: one tile of 2 reduction steps (never split); one tile of
+# 9 steps (2 slices); 2 x 33 tiles of one step (4 x 66 tiles pass the CU count: hoisted)
+AUTO_CASES = {(17, 80, 320): SINGLE, (128, 528, 256): SLICED, (129, 64, 8448): HOISTED}
+
+
+@pytest.mark.parametrize("dtype", (F16, BF), ids=("f16", "bf16"))
+@pytest.mark.parametrize("compact", (False, True), ids=("exact", "compact"))
+@pytest.mark.parametrize("M,N,K", tuple(AUTO_CASES))
+def test_auto_is_the_forced_schedule_it_reports_bit_for_bit(dev, lib, M, N, K, compact, dtype):
+    """Whichever schedule the rule names, "auto" gives the bits of that schedule forced -- the hoisted one those of the dense
+    product it is defined as -- within the fp64 bound of the forced schedules' own tests."""
+    from mxq_amd import packing
+    fn = packing.linear_grad_input if dtype == F16 else packing.linear_grad_input_bf16
+    p = packed(dev, N, K, compact)
+    dy = grads(M, N, dev, dtype, seed=13)
+    sched = lib.mxq_linear_grad_input_schedule(M, N, K, 3 if compact else 0, lib.mxq_gemm_workspace_bytes(), 2 * N * K)
+    if torch.cuda.get_device_properties(dev).multi_processor_count == 256:
+        assert sched == AUTO_CASES[(M, N, K)]
+    auto = fn(dy, p)
+    assert torch.equal(bits(auto), bits(fn(dy, p, path={SINGLE: "single", SLICED: "slices", HOISTED: "hoisted"}[sched])))
+    if sched == HOISTED:
+        dense = packing.linear_dense(dy, packing.dequant_t(p)) if dtype == F16 else \
+            packing.linear_dense_bf16(dy, packing.dequant_t_bf16(p))
+        assert torch.equal(bits(auto), bits(dense))
+    if dtype == F16:
+        G.check_bound(auto, *G.reference(dy, packing.dequant(p).t()), tau=2.0 ** -12, what=f"auto {M}x{N}->{K}")
+    else:
+        check_bound_bf16(auto, dy, packing.dequant_bf16(p), N, f"auto bf16 {M}x{N}->{K}")
+    if N % 64 != 0:                                                  # a partial reduction step: not hoistable
+        with pytest.raises(ValueError):
+            fn(dy, p, path="hoisted")
+    packing.workspace_status(dev)

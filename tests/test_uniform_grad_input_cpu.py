@@ -96,6 +96,18 @@ def test_rejections_before_any_launch(lib, layout):
     assert sliced(S=0, ws=None, nbytes=0) == E_SHAPE
     assert sliced(S=65, nbytes=1 << 40) == E_SHAPE
     assert sliced(ws=P + 8) == E_ALIGN
+    # which error wins: slices without a workspace before every other check; the slice range after the alignment
+    for kw in (dict(M=0), dict(N=4088), dict(lay=7), dict(dy=P + 8), dict(S=65)):
+        assert sliced(ws=None, nbytes=0, **kw) == E_NULL, kw
+    for S in (0, 65):
+        assert sliced(S=S, nbytes=1 << 40, dy=P + 8) == E_ALIGN
+        assert sliced(S=S, nbytes=1 << 40, ws=P + 8) == E_ALIGN
+        assert sliced(S=S, nbytes=1 << 40, M=0) == E_SHAPE
+    for f in (plain, auto):
+        assert f(ws=P, nbytes=need - 1, dy=P + 8) == E_SHAPE           # too small a workspace: before the alignment
+    assert auto(ws=P + 8, nbytes=need - 1, scratch=P + 8, sbytes=big) == E_SHAPE
+    assert auto(M=0, scratch=P + 8, sbytes=big) == E_SHAPE             # the scratch's alignment comes last
+    assert auto(dy=P + 8, scratch=None, sbytes=big) == E_ALIGN
     assert hoisted(scratch=None) == E_NULL                             # hoisted without a scratch
     assert hoisted(scratch=None, M=0) == E_NULL
     for kw in (dict(N=4112), dict(N=272), dict(nbytes=big - 1), dict(nbytes=0)):   # N % 64 != 0; a short scratch

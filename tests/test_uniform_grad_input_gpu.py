@@ -191,6 +191,9 @@ def test_auto_is_the_forced_schedule_it_reports(dev, lib, layout, M, N, K):
     assert torch.equal(_bits(auto), _bits(packing.linear_grad_input(dy, p, path="auto")))
     r, s = G.reference(dy, w16.t())
     G.check_bound(auto, r, s, tau=TAU, what=f"auto = {name} {layout} {M}x{N}->{K}")
+    if N % 64 != 0:                                             # a partial reduction step: not hoistable
+        with pytest.raises(ValueError):
+            packing.linear_grad_input(dy, p, path="hoisted")
     # the three cases reach the three schedules (a 256-CU part: 1 tile, 1 tile of 9 steps, 66 tiles)
     if torch.cuda.get_device_properties(dev).multi_processor_count == 256:
         assert name == {(17, 80, 320): "single", (128, 528, 256): "sliced", (130, 64, 8448): "hoisted"}[(M, N, K)]
