@@ -1,6 +1,6 @@
 // Transposing dequant: packed MXQ (any layout of mxq_format.h; bf16 on the mixed ones only) -> W'^T as a dense 16-bit [K, N] matrix, every
-// element bit-identical to what the dequant / expand kernels of pack.hip write at [n, k] (mxq_dequant.h: fp32 s * (q - z), one
-// rounding to fp16 or bf16).  The first half of the input gradient's hoisted schedule (capi.hip:
+// element bit-identical to what the dequant / expand kernels of pack.hip write at [n, k] (mxq_dequant.h: the ladder of mxq_deq_slot
+// written out below; fp32 s * (q - z), one rounding to fp16 or bf16).  The first half of the input gradient's hoisted schedule (capi.hip:
 // mxq_linear_grad_input_*_hoisted): the dense kernels compute x . w^T with w contiguous along the reduction, and for
 // dx = dy . W' the reduction runs over N, so they need W'^T.
 //

@@ -16,8 +16,8 @@
 // (4 row-blocks x 4 chunks; the forward's fused GEMM dequantises the same 16 blocks per 256 x 128 x 64 step).  A step:
 //   1. the raw blocks (+ the 64 rows' rowmeta) and the dy tile, loaded into registers during the previous step, are
 //      written to LDS, and the next step's loads are issued;
-//   2. every wave dequantises 4 x 8 rows of one block half (mxq_dequant.h, the arithmetic of mxq_dequant_f16_kernel:
-//      bit-exact) into the row-major W' tile;
+//   2. every wave dequantises 4 x 8 rows of one block half (the ladder of mxq_deq_slot, mxq_dequant.h, written out here:
+//      bit-exact with mxq_dequant_f16_kernel, which calls it) into the row-major W' tile;
 //   3. every wave runs its 64 x 64 sub-tile: 2 reduction steps of 32 x 4 x 4 v_mfma_f32_16x16x32_f16.
 // No wave specialisation (150 VGPRs: one workgroup per CU; a 4-wave-per-SIMD budget of 128 spills).
 //
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(DX_THREADS) void mxq_gemm_dx_kernel(const uint16_t*
         __syncthreads();
 
         // 2. dequant: wave w, pass i -> block b = (4w + i) >> 1 (row-block b >> 2, chunk b & 3), rows 8 * (i & 1) + 0..7;
-        //    lane -> (row lane >> 3, 16-byte slot lane & 7), exactly mxq_dequant_f16_kernel's element mapping
+        //    lane -> (row lane >> 3, 16-byte slot lane & 7), the ladder of mxq_deq_slot (mxq_dequant.h) written out
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int combo = wave * 4 + i, b = combo >> 1;
@@ -215,20 +215,6 @@ __global__ __launch_bounds__(DX_THREADS) void mxq_gemm_dx_kernel(const uint16_t*
     }
 }
 
-// dx = fp16 / bf16 (sum over z in order of slab[z]), four elements per thread (M * K % 4 == 0: K % 64 == 0)
-template <bool BF16>
-__global__ __launch_bounds__(256) void mxq_gemm_dx_combine_kernel(const float4* __restrict__ slab, uint2* __restrict__ dx,
-                                                                  int64_t n4, int S) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n4) return;
-    float4 a = slab[i];
-    for (int z = 1; z < S; ++z) {
-        const float4 b = slab[(int64_t)z * n4 + i];
-        a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
-    }
-    dx[i] = make_uint2(mxq_pack16<BF16>(a.x, a.y), mxq_pack16<BF16>(a.z, a.w));
-}
-
 template <int LAYOUT, bool BF16>
 int launch(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K, void* slab, int S,
            hipStream_t stream) {
@@ -244,10 +230,7 @@ int launch(const void* dy, const void* qweight, const void* rowmeta, void* dx, i
     mxq_gemm_dx_kernel<LAYOUT, true, BF16><<<dim3(tiles, S), DX_THREADS, 0, stream>>>(
         (const uint16_t*)dy, (const uint32_t*)qweight, (const float4*)rowmeta, nullptr, (float*)slab, M, N, K, tiles_k,
         per);
-    const int64_t n4 = (int64_t)M * K / 4;
-    mxq_gemm_dx_combine_kernel<BF16><<<dim3((unsigned)((n4 + 255) / 256)), 256, 0, stream>>>((const float4*)slab, (uint2*)dx,
-                                                                                       n4, S);
-    return (int)hipGetLastError();
+    return mxq_launch_slab_combine(slab, dx, (int64_t)M * K / 4, S, BF16, stream);   // M * K % 4 == 0: K % 64 == 0
 }
 
 }   // namespace
@@ -259,17 +242,31 @@ int mxq_launch_gemm_dx_uniform_f16(const void* dy, const void* qweight, const vo
                                       : launch<MXQ_LAYOUT_W4ROW, false>(dy, qweight, rowmeta, dx, M, N, K, slab, slices, stream);
 }
 #else
+// out = fp16 / bf16 (sum over z in order of slab[z]): the combine launch of every sliced schedule here and in linear_bf16.hip,
+// four elements per thread
+template <bool BF16>
+__global__ __launch_bounds__(256) void mxq_slab_combine_kernel(const float4* __restrict__ slab, uint2* __restrict__ out,
+                                                               int64_t n4, int S) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n4) return;
+    float4 a = slab[i];
+    for (int z = 1; z < S; ++z) {
+        const float4 b = slab[(int64_t)z * n4 + i];
+        a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+    }
+    out[i] = make_uint2(mxq_pack16<BF16>(a.x, a.y), mxq_pack16<BF16>(a.z, a.w));
+}
+
+int mxq_launch_slab_combine(const void* slab, void* out, int64_t n4, int S, bool bf16, hipStream_t stream) {
+    const dim3 grid((unsigned)((n4 + 255) / 256));
+    if (bf16) mxq_slab_combine_kernel<true><<<grid, 256, 0, stream>>>((const float4*)slab, (uint2*)out, n4, S);
+    else mxq_slab_combine_kernel<false><<<grid, 256, 0, stream>>>((const float4*)slab, (uint2*)out, n4, S);
+    return (int)hipGetLastError();
+}
+
 int mxq_gemm_dx_slices(int M, int N, int K, size_t slab_bytes) {
     const int tiles = ((M + DX_BM - 1) / DX_BM) * ((K + DX_BK - 1) / DX_BK);
-    const int steps = (N + DX_BN - 1) / DX_BN;
-    const size_t per_slice = (size_t)M * K * 4;
-    // fill the chip: one workgroup per CU, at least 4 reduction steps (256 rows of W') per slice, at most 16 slices
-    const int cus = mxq_cu_count();
-    if (tiles >= cus) return 1;
-    int S = (cus + tiles - 1) / tiles;
-    S = min(S, min(steps / 4, 16));
-    S = (int)min((size_t)S, slab_bytes / per_slice);
-    return S < 2 ? 1 : S;
+    return mxq_fill_slices(tiles, (N + DX_BN - 1) / DX_BN, (size_t)M * K * 4, slab_bytes);
 }
 
 int mxq_launch_gemm_dx_f16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,

@@ -8,8 +8,8 @@
 // BM = 32 for decode-sized calls (wave sub-tile 32 x 32, 1 x 8 waves).  A step:
 //   1. the raw blocks and the x tile, loaded into registers during the previous step, are written to LDS, and the next
 //      step's loads are issued;
-//   2. every wave dequantises 4 x 8 rows of one block half (mxq_dequant.h, the arithmetic of mxq_dequant_bf16_kernel:
-//      bit-exact) into the W' tile;
+//   2. every wave dequantises 4 x 8 rows of one block half (the mixed arms of mxq_deq_slot, mxq_dequant.h, written out here:
+//      bit-exact with mxq_dequant_bf16_kernel, which calls it) into the W' tile;
 //   3. every wave runs its sub-tile: 2 reduction steps of 32 with v_mfma_f32_16x16x32_bf16.
 // The 4-bit arm's per-row parameters (rowmeta) of the tile's 256 rows are read once, before the loop.
 //
@@ -21,8 +21,8 @@
 // own W' row alone, so whatever LDS holds there reaches no stored value.
 //
 // Schedules: whole tiles (grid = tiles, the whole K reduction per workgroup, no workspace) and K slices (grid = tiles x S,
-// slice z reduces steps [z * per, (z + 1) * per) into an fp32 slab [z][M][N] beyond the workspace head, and a combine
-// launch sums the slabs in slice order).  Both are run-to-run deterministic; the workspace head is never touched.
+// slice z reduces steps [z * per, (z + 1) * per) into an fp32 slab [z][M][N] beyond the workspace head, and the combine
+// launch of gemm_dx.hip sums the slabs in slice order).  Both are run-to-run deterministic; the workspace head is never touched.
 #include <hip/hip_runtime.h>
 
 #include "../../include/mxq_hip.h"
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(LB_THREADS) void mxq_linear_bf16_kernel(const uint1
         __syncthreads();
 
         // 2. dequant: wave w, pass i -> row-block b = (4w + i) >> 1 of the tile, rows 8 * (i & 1) + 0..7;
-        //    lane -> (row lane >> 3, 16-byte slot lane & 7), exactly mxq_dequant_bf16_kernel's element mapping
+        //    lane -> (row lane >> 3, 16-byte slot lane & 7), the mixed arms of mxq_deq_slot (mxq_dequant.h) written out
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int combo = wave * 4 + i, b = combo >> 1;
@@ -173,19 +173,6 @@ __global__ __launch_bounds__(LB_THREADS) void mxq_linear_bf16_kernel(const uint1
     }
 }
 
-// y = bf16(sum over z in order of slab[z]), four elements per thread (M * N % 4 == 0: N % 16 == 0)
-__global__ __launch_bounds__(256) void mxq_linear_bf16_combine_kernel(const float4* __restrict__ slab, uint2* __restrict__ y,
-                                                                      int64_t n4, int S) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n4) return;
-    float4 a = slab[i];
-    for (int z = 1; z < S; ++z) {
-        const float4 b = slab[(int64_t)z * n4 + i];
-        a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
-    }
-    y[i] = make_uint2(mxq_pack_bf16(a.x, a.y), mxq_pack_bf16(a.z, a.w));
-}
-
 template <int BM, bool COMPACT>
 int launch(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K, void* slab, int S,
            hipStream_t stream) {
@@ -200,25 +187,14 @@ int launch(const void* x, const void* qweight, const void* rowmeta, void* y, int
     const int per = (steps + S - 1) / S;
     mxq_linear_bf16_kernel<BM, COMPACT, true><<<dim3(tiles, S), LB_THREADS, 0, stream>>>(
         (const uint16_t*)x, (const uint32_t*)qweight, (const float4*)rowmeta, nullptr, (float*)slab, M, N, K, tiles_n, per);
-    const int64_t n4 = (int64_t)M * N / 4;
-    mxq_linear_bf16_combine_kernel<<<dim3((unsigned)((n4 + 255) / 256)), 256, 0, stream>>>((const float4*)slab, (uint2*)y,
-                                                                                           n4, S);
-    return (int)hipGetLastError();
+    return mxq_launch_slab_combine(slab, y, (int64_t)M * N / 4, S, true, stream);   // M * N % 4 == 0: N % 16 == 0
 }
 
 }   // namespace
 
 int mxq_linear_bf16_slices(int bm, int M, int N, int K, size_t slab_bytes) {
     const int tiles = ((M + bm - 1) / bm) * ((N + LB_BN - 1) / LB_BN);
-    const int steps = K / 64;
-    const size_t per_slice = (size_t)M * N * 4;
-    // fill the chip: one workgroup per CU, at least 4 reduction steps (256 columns of W') per slice, at most 16 slices
-    const int cus = mxq_cu_count();
-    if (tiles >= cus) return 1;
-    int S = (cus + tiles - 1) / tiles;
-    S = min(S, min(steps / 4, 16));
-    S = (int)min((size_t)S, slab_bytes / per_slice);
-    return S < 2 ? 1 : S;
+    return mxq_fill_slices(tiles, K / 64, (size_t)M * N * 4, slab_bytes);
 }
 
 // Measured (profiles/bf16_linear_bench.txt): the 128-token tile sliced in K stays ahead of dequant + dense while one wave of

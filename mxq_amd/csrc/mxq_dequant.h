@@ -126,6 +126,42 @@ MXQ_HD void mxq_deq4x8(uint32_t d, float s, float z, uint32_t out[4]) {
     out[3] = mxq_pack16<BF16>(s * (mxq_ubyte2(m1) - z), s * (mxq_ubyte3(m1) - z));
 }
 
+#if defined(__HIPCC__) || defined(MXQ_HOST_HALF)
+// The dequant FRONT of the kernels that write or multiply W' as 16-byte slots: one 16-row block `blk` of layout LAYOUT
+// (mxq_format.h), row r of it, 16-byte slot `slot` (0..7) of the row's 128-byte chunk line -> the slot's 8 weights as 4 packed
+// 16-bit pairs, out[i] = columns (8 slot + 2i, 8 slot + 2i + 1) of the chunk.  qt = slot >> 1 is the 16-column quarter (the
+// 2-bit group, where the quarter is one), h = slot & 1 the half of it:
+//   W2G16          all four quarters are 2-bit groups: the LUT of mxq_deq2x8, scale nibble qt of SC, QQ slot qt;
+//   W4ROW          4-bit codes of (quarter, half) with the row's one scale and zero-point;
+//   mixed, qt < 3  the 2-bit LUT, the group's fields through MxqMixed<COMPACT>;
+//   mixed, qt = 3  the 4-bit arm: half h of C4 with the row's scale and zero-point.
+// `rowmeta()` returns the row's {zero, scale code, qs, qz} as .x .y .z .w from wherever the caller keeps it; it is called on
+// the 4-bit branches alone, so a W2G16 caller reads none.  The bit-exactness contract of W': the plain dequant (pack.hip) calls
+// this and tests/host_emu.cpp walks it on the CPU.  The transposing pass (dequant_t.hip), the fused dX (gemm_dx.hip) and the
+// bf16 forward (linear_bf16.hip) keep the same ladder written out in their step 2 -- through this call they measured slower
+// at some points (profiles/dequant_front_ab.txt) -- and tests/test_dequant_front_gpu.py holds each of them to the plain
+// dequant bit for bit.
+template <int LAYOUT, bool BF16, class RM>
+MXQ_HD void mxq_deq_slot(const uint32_t* blk, RM&& rowmeta, int r, int slot, uint32_t out[4]) {
+    typedef MxqMixed<LAYOUT == MXQ_LAYOUT_MIXEDC> F;
+    const int qt = slot >> 1, h = slot & 1;
+    if (LAYOUT == MXQ_LAYOUT_W2G16 || (LAYOUT != MXQ_LAYOUT_W4ROW && qt < 3)) {
+        constexpr bool W2 = LAYOUT == MXQ_LAYOUT_W2G16;
+        const uint32_t d = blk[W2 ? mxq_w2_c2(qt, r) : mxq_c2(qt, r)];
+        float z;
+        if constexpr (W2) z = __builtin_bit_cast(float, blk[mxq_w2_z2(qt, r)]);
+        else z = F::z2(blk, qt, r);
+        const uint32_t scw = F::scw(blk, r);      // (W2G16 keeps SC and QQ where the exact mixed layout does)
+        const float qs = __builtin_bit_cast(float, blk[F::qq(qt)]), qz = __builtin_bit_cast(float, blk[F::qq(qt) + 1]);
+        mxq_deq2x8<BF16>(d, h, mxq_scale(qs, qz, (scw >> (4 * qt)) & 15u), z, out);
+    } else {
+        const auto m = rowmeta();
+        const uint32_t d = blk[LAYOUT == MXQ_LAYOUT_W4ROW ? mxq_w4_c4(qt, h, r) : mxq_c4(h, r)];
+        mxq_deq4x8<BF16>(d, mxq_scale(m.z, m.w, (uint32_t)m.y), m.x, out);
+    }
+}
+#endif
+
 // Integer unpack (the bit-exact contract of the unpack kernel)
 MXQ_HD uint32_t mxq_code2(uint32_t d, int k) { return (d >> mxq_bit2(k)) & 3u; }
 MXQ_HD uint32_t mxq_code4(uint32_t d, int k) { return (d >> mxq_bit4(k)) & 15u; }

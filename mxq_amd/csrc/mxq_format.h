@@ -103,6 +103,11 @@ MXQ_HD bool mxq_layout_is_mixed(int layout) { return layout == MXQ_LAYOUT_MIXED 
 #if defined(__HIPCC__) || defined(MXQ_HOST_HALF)
 // Field access of the two metadata modes of the mixed layout behind one interface (C2 / C4 sit at the same
 // offsets in both): zero-point as float, the row's scale-code word, the (qs, qz) dword offset.
+#if defined(__HIPCC__)
+MXQ_HD float mxq_h2f(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
+#else
+float mxq_h2f(uint16_t h);   // fp16 bits -> float, provided by the host harness (tests/host_emu.cpp)
+#endif
 template <bool COMPACT>
 struct MxqMixed {
     static constexpr int BLK_DW = COMPACT ? MXQC_BLK_DW : MXQ_BLK_DW;
@@ -111,16 +116,10 @@ struct MxqMixed {
         return ((const uint16_t*)tile)[COMPACT ? mxqc_sc_u16(r) : mxq_sc_u16(r)];
     }
     static MXQ_HD int qq(int g) { return COMPACT ? mxqc_qq(g) : mxq_qq(g); }
-#if defined(__HIPCC__)
-    static __device__ __forceinline__ float z2(const uint32_t* tile, int g, int r) {
-        if constexpr (COMPACT) {
-            const uint16_t h = ((const uint16_t*)tile)[mxqc_z2_u16(g, r)];
-            return (float)__builtin_bit_cast(_Float16, h);
-        } else {
-            return __builtin_bit_cast(float, tile[mxq_z2(g, r)]);
-        }
+    static MXQ_HD float z2(const uint32_t* tile, int g, int r) {
+        if constexpr (COMPACT) return mxq_h2f(((const uint16_t*)tile)[mxqc_z2_u16(g, r)]);
+        else return __builtin_bit_cast(float, tile[mxq_z2(g, r)]);
     }
-#endif
 };
 #endif
 MXQ_HD int mxq_w2_c2(int g, int r) { return g * 16 + r; }

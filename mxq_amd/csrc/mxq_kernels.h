@@ -133,6 +133,18 @@ inline int mxq_cu_count() {
     if (slot) cached[dev].store(n, std::memory_order_relaxed);
     return n;
 }
+
+// The slices of a sliced schedule (gemm_dx.hip over N, linear_bf16.hip over K) of `tiles` output tiles and `steps` reduction
+// steps, each slice writing a `bytes_per_slice` fp32 slab into `slab_bytes`: fill the chip -- one workgroup per CU -- with at
+// least 4 reduction steps (256 rows or columns of W') per slice and at most 16 slices, as far as the slab holds.  1: none.
+inline int mxq_fill_slices(int tiles, int steps, size_t bytes_per_slice, size_t slab_bytes) {
+    const int cus = mxq_cu_count();
+    if (tiles >= cus) return 1;
+    int S = (cus + tiles - 1) / tiles;
+    S = min(S, min(steps / 4, 16));
+    S = (int)min((size_t)S, slab_bytes / bytes_per_slice);
+    return S < 2 ? 1 : S;
+}
 #endif
 // the same product with a 256 x 256 tile and a quadrant-phase ping-pong schedule (dense256.hip); MXQ_NOT_MY_SHAPE: odd
 // K-tile count, or -- unless force -- too few tiles to fill the chip twice: take the kernel above
@@ -214,8 +226,12 @@ int mxq_launch_gemv_proto_f16(const void* x, const void* weight, const void* wei
                               const void* scales_4b, const void* zeros_4b, void* y, int B, int IC, int OC,
                               hipStream_t stream);
 // gemm_dx.hip: the quantised Linear's input gradient (mixed layout, exact or compact metadata); `slices` <= 1: one launch
-// of whole tiles, else `slices` N-slices into fp32 slabs at `slab` (slices * M * K * 4 bytes) and a combine launch
+// of whole tiles, else `slices` N-slices into fp32 slabs at `slab` (slices * M * K * 4 bytes) and a combine launch.
+// mxq_gemm_dx_slices: the slices that fill the chip with `slab_bytes` of slab (1: none; the rule is mxq_fill_slices)
 int mxq_gemm_dx_slices(int M, int N, int K, size_t slab_bytes);
+// the combine launch of the sliced schedules of gemm_dx.hip and linear_bf16.hip: out[i] = fp16 / bf16 of the sum over z, in
+// order, of the S fp32 slabs slab[z][i]; n4 = elements / 4 (defined in gemm_dx.hip)
+int mxq_launch_slab_combine(const void* slab, void* out, int64_t n4, int S, bool bf16, hipStream_t stream);
 int mxq_launch_gemm_dx_f16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,
                            int layout, void* slab, int slices, hipStream_t stream);
 int mxq_launch_gemm_dx_bf16(const void* dy, const void* qweight, const void* rowmeta, void* dx, int M, int N, int K,

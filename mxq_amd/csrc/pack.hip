@@ -88,8 +88,8 @@ __global__ void mxq_unpack_kernel(const uint32_t* __restrict__ qweight, const fl
 // ------------------------------------------------------------------------------------ //
 // dequant to a dense fp16 [N, K] matrix (bit-exact fake-quant weight, mxqgpt.py:448): the first half of the
 // hoisted mode.  Write-bound (2 B out per 0.56 B in), so the layout follows the STORES: a lane owns one 16-byte
-// slot (8 weights = half a 16-column quarter) of a row's 128-byte chunk line, 8 lanes cover the line and a wave
-// instruction writes 8 rows x 128 B in full lines.  (Round 2's thread -> (row, quarter) mapping wrote 32-byte
+// slot (8 weights = half a 16-column quarter: mxq_deq_slot, mxq_dequant.h) of a row's 128-byte chunk line, 8 lanes cover
+// the line and a wave instruction writes 8 rows x 128 B in full lines.  (Round 2's thread -> (row, quarter) mapping wrote 32-byte
 // pieces of 16 different rows per instruction: 13.0 -> 9.6 us at 4096^2, profiles/r03_dense256.txt.)
 // Block = 4 waves = the 4 chunks of a chunk quad x one 16-row block; a wave does its chunk's rows 0-7, then 8-15.
 // ------------------------------------------------------------------------------------ //
@@ -101,23 +101,14 @@ __device__ __forceinline__ void dequant_rows(const uint32_t* __restrict__ qweigh
     const int lane = threadIdx.x & 63;
     const int c = c4 * 4 + (threadIdx.x >> 6);          // wave-uniform
     if (c >= NC) return;
-    const int slot = lane & 7, qt = slot >> 1, h = slot & 1;
-    typedef MxqMixed<COMPACT> F;
-    const uint32_t* tile = qweight + ((int64_t)rb * NC + c) * F::BLK_DW;
+    const int slot = lane & 7;
+    constexpr int LAYOUT = COMPACT ? MXQ_LAYOUT_MIXEDC : MXQ_LAYOUT_MIXED;
+    const uint32_t* tile = qweight + ((int64_t)rb * NC + c) * MxqMixed<COMPACT>::BLK_DW;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int r = i * 8 + (lane >> 3), n = rb * 16 + r;
         uint32_t o[4];
-        if (qt < 3) {
-            const uint32_t d = tile[mxq_c2(qt, r)];
-            const float z = F::z2(tile, qt, r);
-            const uint32_t scw = F::scw(tile, r);
-            const float qs = __uint_as_float(tile[F::qq(qt)]), qz = __uint_as_float(tile[F::qq(qt) + 1]);
-            mxq_deq2x8<BF16>(d, h, mxq_scale(qs, qz, (scw >> (4 * qt)) & 15u), z, o);
-        } else {
-            const float4 m = rowmeta[n];
-            mxq_deq4x8<BF16>(tile[mxq_c4(h, r)], mxq_scale(m.z, m.w, (uint32_t)m.y), m.x, o);
-        }
+        mxq_deq_slot<LAYOUT, BF16>(tile, [&] { return rowmeta[n]; }, r, slot, o);
         *(uint4*)(out + (int64_t)n * K + c * 64 + slot * 8) = make_uint4(o[0], o[1], o[2], o[3]);
     }
 }

@@ -9,9 +9,30 @@
 
 uint16_t mxq_host_f32_to_f16(float f) { return _cvtss_sh(f, _MM_FROUND_TO_NEAREST_INT | _MM_FROUND_NO_EXC); }
 
+float mxq_h2f(uint16_t h) { return _cvtsh_ss(h); }
+
+#define MXQ_HOST_HALF 1   // MxqMixed and mxq_deq_slot (the emulation has entries for the exact metadata and the uniform layouts)
 #include "../mxq_amd/csrc/mxq_dequant.h"
 #include "../mxq_amd/csrc/mxq_format.h"
 #include "../mxq_amd/csrc/mxq_pack.h"
+
+// The row's rowmeta as mxq_deq_slot reads it (the device passes a float4)
+struct RowMeta { float x, y, z, w; };
+
+// dequantise by walking (row, 16-byte slot) through mxq_deq_slot: the per-thread code of mxq_dequant_f16_kernel, and the
+// ladder that the transposing pass, the fused dX and the bf16 forward write out
+template <int LAYOUT>
+static void dequant_f16(const uint32_t* qweight, const float* rowmeta, uint16_t* out, int N, int K) {
+    const int NC = K / 64, BLK_DW = mxq_layout_blk_dw(LAYOUT);
+    for (int n = 0; n < N; ++n)
+        for (int c = 0; c < NC; ++c)
+            for (int slot = 0; slot < 8; ++slot) {
+                uint32_t o[4];
+                mxq_deq_slot<LAYOUT, false>(qweight + mxq_blk_index(n, c, K) * BLK_DW,
+                                            [&] { return ((const RowMeta*)rowmeta)[n]; }, n & 15, slot, o);
+                memcpy(out + (long)n * K + c * 64 + slot * 8, o, 16);
+            }
+}
 
 extern "C" {
 
@@ -49,28 +70,36 @@ void emu_unpack(const uint32_t* qweight, uint8_t* codes2, uint8_t* sc2, float* z
                                  zero2 + (long)n * NC * 3 + c * 3, codes4 + (long)n * NC * 16 + c * 16);
 }
 
-// dequantise with exactly the per-thread code of mxq_dequant_f16_kernel / the GEMM staging
 void emu_dequant_f16(const uint32_t* qweight, const float* rowmeta, uint16_t* out, int N, int K) {
-    const int NC = K / 64;
+    dequant_f16<MXQ_LAYOUT_MIXED>(qweight, rowmeta, out, N, K);
+}
+
+// the uniform layouts: pack the oracle's parameters (codes [N, K]; W2G16: sc / zero [N, K/16], qs / qz [N/16, K/16]; W4ROW:
+// everything but the codes is the caller's rowmeta) into blocks, and dequantise them through the same front
+void emu_pack_uniform(const uint8_t* codes, const uint8_t* sc, const float* zero, const float* qs, const float* qz,
+                      uint32_t* qweight, int N, int K, int layout) {
+    const int NC = K / 64, G = K / 16, BLK_DW = mxq_layout_blk_dw(layout);
+    memset(qweight, 0, (size_t)(N / 16) * NC * BLK_DW * 4);
     for (int n = 0; n < N; ++n)
-        for (int c = 0; c < NC; ++c) {
-            const uint32_t* tile = qweight + mxq_blk_index(n, c, K) * MXQ_BLK_DW;
-            const int r = n & 15;
-            uint32_t o[8];
-            const uint32_t scw = ((const uint16_t*)tile)[mxq_sc_u16(r)];
-            for (int g = 0; g < 3; ++g) {
-                float qs, qz, z;
-                memcpy(&qs, tile + mxq_qq(g), 4);
-                memcpy(&qz, tile + mxq_qq(g) + 1, 4);
-                memcpy(&z, tile + mxq_z2(g, r), 4);
-                mxq_deq2x16(tile[mxq_c2(g, r)], mxq_scale(qs, qz, (scw >> (4 * g)) & 15u), z, o);
-                memcpy(out + (long)n * K + c * 64 + g * 16, o, 32);
+        for (int c = 0; c < NC; ++c)
+            for (int qt = 0; qt < 4; ++qt) {
+                uint32_t* blk = qweight + mxq_blk_index(n, c, K) * BLK_DW;
+                const uint8_t* q = codes + (long)n * K + c * 64 + qt * 16;
+                const int r = n & 15, g = c * 4 + qt;
+                if (layout == MXQ_LAYOUT_W4ROW) {
+                    for (int k = 0; k < 16; ++k) blk[mxq_w4_c4(qt, k >> 3, r)] |= (uint32_t)q[k] << mxq_bit4(k & 7);
+                    continue;
+                }
+                for (int k = 0; k < 16; ++k) blk[mxq_w2_c2(qt, r)] |= (uint32_t)q[k] << mxq_bit2(k);
+                memcpy(blk + mxq_w2_z2(qt, r), zero + (long)n * G + g, 4);
+                ((uint16_t*)blk)[mxq_sc_u16(r)] |= (uint16_t)(sc[(long)n * G + g] << (4 * qt));
+                memcpy(blk + mxq_qq(qt), qs + (long)(n / 16) * G + g, 4);
+                memcpy(blk + mxq_qq(qt) + 1, qz + (long)(n / 16) * G + g, 4);
             }
-            const float* m = rowmeta + 4 * n;
-            const float s4 = mxq_scale(m[2], m[3], (uint32_t)m[1]);
-            mxq_deq4x8(tile[mxq_c4(0, r)], s4, m[0], o);
-            mxq_deq4x8(tile[mxq_c4(1, r)], s4, m[0], o + 4);
-            memcpy(out + (long)n * K + c * 64 + 48, o, 32);
-        }
+}
+
+void emu_dequant_uniform_f16(const uint32_t* qweight, const float* rowmeta, uint16_t* out, int N, int K, int layout) {
+    if (layout == MXQ_LAYOUT_W2G16) dequant_f16<MXQ_LAYOUT_W2G16>(qweight, rowmeta, out, N, K);
+    else dequant_f16<MXQ_LAYOUT_W4ROW>(qweight, rowmeta, out, N, K);
 }
 }

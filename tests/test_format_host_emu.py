@@ -116,3 +116,41 @@ def test_property_pack_unpack_dequant(emu, seed, nc, rb, zscale, sscale):
     with np.errstate(over="ignore", invalid="ignore"):
         w16 = O.mxq_dequant(p).astype(np.float16)       # overflow to inf is part of the contract (one rounding)
     _roundtrip_and_dequant(emu, p, N, K, w16)
+
+
+# ----------------------------------------------------------------------------------------
+# the uniform layouts through the same dequant front (mxq_deq_slot): the oracle's parameters packed into W2G16 / W4ROW
+# blocks on the host dequantise to the oracle's weight rounded once to fp16, bit for bit
+# ----------------------------------------------------------------------------------------
+def _uniform_dequant(emu, p, N, K, layout):
+    code = {"w2g16": 1, "w4row": 2}[layout]
+    qw = np.zeros((N // 16) * (K // 64) * (144 if layout == "w2g16" else 128), np.uint32)
+    arrs = [np.ascontiguousarray(p[k]) for k in ("codes", "sc", "zero", "qs", "qz")]
+    emu.emu_pack_uniform(*[_ptr(a) for a in arrs], _ptr(qw), N, K, code)
+    rm = np.zeros((N, 4), np.float32)
+    if layout == "w4row":                                     # {zero, scale code, qs, qz} per row
+        for j, k in enumerate(("zero", "sc", "qs", "qz")):
+            col = np.asarray(p[k], np.float32).reshape(-1)
+            rm[:, j] = col if col.size == N else np.repeat(col, N // col.size)
+    out = np.zeros((N, K), np.uint16)
+    emu.emu_dequant_uniform_f16(_ptr(qw), _ptr(rm), _ptr(out), N, K, code)
+    return out
+
+
+@pytest.mark.parametrize("layout,pre", [("w2g16", "w2"), ("w4row", "w4")])
+def test_g8_uniform_dequant(emu, layout, pre):
+    from tests.conftest import load_golden
+    g8 = load_golden("g8_uniform.npz")
+    N, K = g8["W"].shape
+    p = {k: g8[f"{pre}_{k}"] for k in ("codes", "sc", "zero", "qs", "qz")}
+    assert np.array_equal(_uniform_dequant(emu, p, N, K, layout), g8[f"{pre}_wdeq"].view(np.uint16))
+
+
+@pytest.mark.parametrize("layout", ["w2g16", "w4row"])
+@pytest.mark.parametrize("N,K,seed", [(32, 64, 0), (48, 320, 1)])
+def test_uniform_random_vs_oracle(emu, layout, N, K, seed):
+    rng = np.random.default_rng(seed)
+    W = rng.standard_normal((N, K)).astype(np.float32) * (0.02 * (1 + np.arange(N, dtype=np.float32)[:, None]))
+    W[0, 48:64] = 0.5        # a constant fourth group
+    p = O.uniform_quantize(W, layout)
+    assert np.array_equal(_uniform_dequant(emu, p, N, K, layout), p["w_deq32"].astype(np.float16).view(np.uint16))
