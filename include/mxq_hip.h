@@ -374,6 +374,27 @@ int mxq_linear_grad_input_f16_layout_auto(const void* dy, const void* qweight, c
                                           int K, int layout, void* workspace, size_t workspace_bytes, void* scratch,
                                           size_t scratch_bytes, void* stream);
 
+/* ---- calibration statistics for the per-layer layout choice ------------------------------------------------------------------
+ * What mxq_amd/lib/layout_search.py measures a packed weight by: with m[k] = E[x_k^2] of the Linear's input, the expected squared
+ * output error E|x (W - W')^T|^2 is, under the diagonal-Hessian approximation this build uses throughout (DESIGN.md section 0
+ * row (f)), sum_n sum_k m[k] (W[n, k] - W'[n, k])^2.  Both entries are single launches that neither allocate nor synchronise
+ * and take no workspace; every sum is fp32 in an order the launch geometry alone fixes (no atomics): two runs are
+ * bit-identical.  Checks, in order: MXQ_E_NULL (x, moment_out; W, qweight, rowmeta, err_rows), MXQ_E_SHAPE (rows <= 0,
+ * K % 64; N % 16, N <= 0, an unknown layout code), MXQ_E_DTYPE, MXQ_E_ALIGN (x, W, qweight, rowmeta: 16 bytes; the float
+ * arrays: 4 bytes).
+ *
+ * mxq_col_moment: moment_out[k] = (moment_in ? moment_in[k] : 0) + sum_r x[r, k]^2 for x [rows, K] row-major of dtype
+ * MXQ_DTYPE_*, read once; moment_in == moment_out accumulates in place.
+ * mxq_quant_error: err_rows[n] = sum_k c[k] (w[n, k] - w'[n, k])^2 and, where ref_rows is given, ref_rows[n] =
+ * sum_k c[k] w[n, k]^2, with w = W [N, K] (dtype MXQ_DTYPE_*) widened to fp32, w' the fp16 weight that the plain dequant of
+ * that layout writes (mxq_dequant_f16, mxq_dequant_f16_compact, mxq_expand_layout: the same register-level front,
+ * csrc/mxq_dequant.h) widened to fp32, and c = col_weight [K] (NULL: all ones).  Every layout code is taken.  W and the blocks
+ * are read once and W' is never written to memory: about 2.56 B / weight for an fp16 W instead of the 8.5 B+ of a dequant
+ * followed by elementwise arithmetic.  A NaN or an infinity in W makes that row's results non-finite. */
+int mxq_col_moment(const void* x, int x_dtype, int64_t rows, int K, const float* moment_in, float* moment_out, void* stream);
+int mxq_quant_error(const void* W, int w_dtype, const void* qweight, const void* rowmeta, const float* col_weight,
+                    float* err_rows, float* ref_rows, int N, int K, int layout, void* stream);
+
 /* Uniform-bit-width layouts for the W2A16 / W4A16 / mixed sweep (BASELINE config 5); the mixed
  * layout is layout 0.  1 = W2G16: Quantizer(bits=2, qq_scale_bits=4) on every 16-column group
  * (quantizer.py:61-147), 4.5 bit/weight; 2 = W4ROW: Quantizer(bits=4, qq_scale_bits=4) per row

@@ -131,6 +131,8 @@ SIGNATURES = {
                                                                          c_void_p]),
     "mxq_linear_grad_input_f16_layout_auto": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
                                                       c_size_t, c_void_p]),
+    "mxq_col_moment": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "mxq_quant_error": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mxq_gemv_proto_f16": (c_int, [c_void_p] * 9 + [c_int, c_int, c_int, c_int, c_void_p]),
 }
 

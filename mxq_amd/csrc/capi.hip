@@ -9,6 +9,7 @@
 namespace {
 inline bool shape_ok(int N, int K) { return N > 0 && K > 0 && N % 16 == 0 && K % 64 == 0; }
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+inline bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
 inline bool dtype_ok(int d) { return d == MXQ_DTYPE_F32 || d == MXQ_DTYPE_F16 || d == MXQ_DTYPE_BF16; }
 inline bool layout_ok(int l) {
     return l == MXQ_LAYOUT_MIXED || l == MXQ_LAYOUT_W2G16 || l == MXQ_LAYOUT_W4ROW || l == MXQ_LAYOUT_MIXEDC;
@@ -98,6 +99,27 @@ int mxq_dequant_bf16(const void* qweight, const void* rowmeta, void* w16, int N,
     if (!shape_ok(N, K) || !mxq_layout_is_mixed(layout)) return MXQ_E_SHAPE;
     if (!aligned16(qweight) || !aligned16(rowmeta) || !aligned16(w16)) return MXQ_E_ALIGN;
     return mxq_launch_dequant_bf16(qweight, rowmeta, w16, N, K, layout == MXQ_LAYOUT_MIXEDC, (hipStream_t)stream);
+}
+
+// the calibration statistics of the layout search (quant_error.hip)
+int mxq_col_moment(const void* x, int x_dtype, int64_t rows, int K, const float* moment_in, float* moment_out, void* stream) {
+    if (!x || !moment_out) return MXQ_E_NULL;
+    if (rows <= 0 || K <= 0 || K % 64 != 0) return MXQ_E_SHAPE;
+    if (!dtype_ok(x_dtype)) return MXQ_E_DTYPE;
+    if (!aligned16(x) || !aligned4(moment_in) || !aligned4(moment_out)) return MXQ_E_ALIGN;
+    return mxq_launch_col_moment(x, x_dtype, rows, K, moment_in, moment_out, (hipStream_t)stream);
+}
+
+int mxq_quant_error(const void* W, int w_dtype, const void* qweight, const void* rowmeta, const float* col_weight,
+                    float* err_rows, float* ref_rows, int N, int K, int layout, void* stream) {
+    if (!W || !qweight || !rowmeta || !err_rows) return MXQ_E_NULL;
+    if (!shape_ok(N, K) || !layout_ok(layout)) return MXQ_E_SHAPE;
+    if (!dtype_ok(w_dtype)) return MXQ_E_DTYPE;
+    if (!aligned16(W) || !aligned16(qweight) || !aligned16(rowmeta) || !aligned4(col_weight) || !aligned4(err_rows) ||
+        !aligned4(ref_rows))
+        return MXQ_E_ALIGN;
+    return mxq_launch_quant_error(W, w_dtype, qweight, rowmeta, col_weight, err_rows, ref_rows, N, K, layout,
+                                  (hipStream_t)stream);
 }
 
 static int linear_check(const void* x, const void* qweight, const void* rowmeta, void* y, int M, int N, int K) {

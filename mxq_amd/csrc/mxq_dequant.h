@@ -136,8 +136,9 @@ MXQ_HD void mxq_deq4x8(uint32_t d, float s, float z, uint32_t out[4]) {
 //   mixed, qt < 3  the 2-bit LUT, the group's fields through MxqMixed<COMPACT>;
 //   mixed, qt = 3  the 4-bit arm: half h of C4 with the row's scale and zero-point.
 // `rowmeta()` returns the row's {zero, scale code, qs, qz} as .x .y .z .w from wherever the caller keeps it; it is called on
-// the 4-bit branches alone, so a W2G16 caller reads none.  The bit-exactness contract of W': the plain dequant (pack.hip) calls
-// this and tests/host_emu.cpp walks it on the CPU.  The transposing pass (dequant_t.hip), the fused dX (gemm_dx.hip) and the
+// the 4-bit branches alone, so a W2G16 caller reads none.  The bit-exactness contract of W': the plain dequant (pack.hip) and the
+// quantisation-error kernel (quant_error.hip, which compares W' with the original weight in registers) call this and
+// tests/host_emu.cpp walks it on the CPU.  The transposing pass (dequant_t.hip), the fused dX (gemm_dx.hip) and the
 // bf16 forward (linear_bf16.hip) keep the same ladder written out in their step 2 -- through this call they measured slower
 // at some points (profiles/dequant_front_ab.txt) -- and tests/test_dequant_front_gpu.py holds each of them to the plain
 // dequant bit for bit.

@@ -28,6 +28,12 @@ int mxq_launch_dequant_t_bf16(const void* qweight, const void* rowmeta, void* ou
 // ... of any layout code (fp16; W2G16 / W4ROW: bit-identical to mxq_launch_uniform_expand's w16, transposed)
 int mxq_launch_dequant_t_f16_layout(const void* qweight, const void* rowmeta, void* out, int N, int K, int layout,
                                     hipStream_t stream);
+// quant_error.hip: the calibration statistics of the layout search -- the column second moment of a Linear's input and the
+// activation-weighted squared error of a packed weight (any layout code) against the weight it came from, row by row
+int mxq_launch_col_moment(const void* x, int dtype, int64_t rows, int K, const float* moment_in, float* moment_out,
+                          hipStream_t stream);
+int mxq_launch_quant_error(const void* W, int dtype, const void* qweight, const void* rowmeta, const float* col_weight,
+                           float* err_rows, float* ref_rows, int N, int K, int layout, hipStream_t stream);
 int mxq_launch_compact(const void* qweight_exact, void* qweight_compact, int N, int K, hipStream_t stream);
 int mxq_launch_quantize_pack(const void* W, int dtype, const uint8_t* dead, void* qweight, void* rowmeta, int N,
                              int K, hipStream_t stream);

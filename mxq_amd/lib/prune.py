@@ -12,6 +12,8 @@ For every layer, as the reference does (prune.py:368-417):
 With ``pack=True`` step 3 additionally swaps each ``nn.Linear`` for a ``QuantLinear`` holding the packed
 weight (4.5 bit/weight in HBM, HIP GEMM / GEMV forward), which is what a serving checkpoint stores
 (mxq_amd/checkpoint.py); the re-run of step 4 then already uses the packed kernels.
+``layout`` picks the packed layout per Linear ("mixed", "w2g16", "w4row": ``QuantLinear``'s), e.g. the choice of
+``lib.layout_search.search_layouts``.
 """
 from __future__ import annotations
 
@@ -47,18 +49,38 @@ def _first(out):
     return out[0] if isinstance(out, (tuple, list)) else out
 
 
+def _layout_of(layout, key: str) -> str:
+    """The layout of the Linear ``key`` = "<layer index>.<linear name>": ``layout`` is a name, a dict or a callable on keys."""
+    if isinstance(layout, str):
+        return layout
+    if callable(layout):
+        return layout(key)
+    if key not in layout:
+        raise ValueError(f"layout has no entry for {key!r}")
+    return layout[key]
+
+
 @torch.no_grad()
 def quantize_sequential(layers: Sequence[nn.Module], inps: torch.Tensor, layer_kwargs: Optional[dict] = None,
                         pack: bool = False, percdamp: float = 0.01, blocksize: int = 16,
-                        log: Optional[Callable[[str], None]] = None) -> Dict[str, object]:
+                        log: Optional[Callable[[str], None]] = None, layout="mixed",
+                        compact: bool = False) -> Dict[str, object]:
     """Quantise ``layers`` in order on the calibration batch ``inps`` [nsamples, seq, hidden].
 
     ``layer_kwargs`` are passed to every layer call (the reference passes ``attention_mask`` and
     ``position_ids``, prune.py:400).  Returns ``{"<layer index>.<linear name>": PackedMXQ}``; the
-    layers are modified in place (fake-quant fp16 weights, or QuantLinear modules when ``pack``)."""
+    layers are modified in place (fake-quant fp16 weights, or QuantLinear modules when ``pack``).
+
+    ``layout``: the packed layout -- one name for every Linear, or a dict or a callable from the returned keys to names (a
+    key missing from a dict: ValueError, before anything is quantised); a "w2g16" / "w4row" Linear comes back as a
+    PackedUniform.  ``compact``: compact metadata on the Linears of the mixed layout."""
     layer_kwargs = dict(layer_kwargs or {})
     if inps.dim() != 3:
         raise ValueError("inps must be [nsamples, seq, hidden]")
+    if not isinstance(layout, str) and not callable(layout):
+        for i, layer in enumerate(layers):
+            for name in find_layers(layer):
+                _layout_of(layout, f"{i}.{name}")
     outs = torch.zeros_like(inps)
     packed: Dict[str, object] = {}
     for i, layer in enumerate(layers):
@@ -80,7 +102,8 @@ def quantize_sequential(layers: Sequence[nn.Module], inps: torch.Tensor, layer_k
         for name, g in gpts.items():
             if log:
                 log(f"{i} {name}")
-            g.fasterquant(percdamp=percdamp, blocksize=blocksize)
+            lay = _layout_of(layout, f"{i}.{name}")
+            g.fasterquant(percdamp=percdamp, blocksize=blocksize, layout=lay, compact=compact and lay == "mixed")
             packed[f"{i}.{name}"] = g.packed
             if pack:
                 _set_submodule(layer, name, QuantLinear.from_packed(g.packed, bias=subset[name].bias))

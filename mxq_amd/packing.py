@@ -897,3 +897,62 @@ def dequant_uniform(p: PackedUniform) -> torch.Tensor:
     """Dense fp16 [N, K] weight of a PackedUniform: ``expand_uniform(p)[0]`` without the code tensors."""
     _need_gpu(p.qweight)
     return expand_uniform(p, codes=False)[0]
+
+
+# ------------------------------------------------------------------------------------------------
+# calibration statistics of the per-layer layout choice (lib/layout_search.py; csrc/quant_error.hip)
+# ------------------------------------------------------------------------------------------------
+def col_moment(x: torch.Tensor, moment: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """sum over all rows of x[..., K]^2 as fp32 [K] (include/mxq_hip.h: mxq_col_moment): the diagonal of the Hessian sum of
+    x x^T of a Linear's input.  x fp16 / bf16 / fp32 on the GPU, in_features % 64 == 0.  ``moment`` (fp32 [K], contiguous, on
+    x's device): accumulated in place and returned.  Deterministic: fp32 sums in a fixed order, no atomics."""
+    _need_gpu(x, moment)
+    if x.dtype not in _TORCH2CODE:
+        raise ValueError(f"unsupported activation dtype {x.dtype}")
+    if x.dim() < 1 or x.shape[-1] <= 0 or x.shape[-1] % 64 != 0:
+        raise ValueError(f"col_moment needs x [..., K] with K % 64 == 0, got {tuple(x.shape)}")
+    K = x.shape[-1]
+    if moment is None:
+        out = torch.empty(K, dtype=torch.float32, device=x.device)
+    elif moment.dtype != torch.float32 or tuple(moment.shape) != (K,) or not moment.is_contiguous() or moment.device != x.device:
+        raise ValueError("moment must be a contiguous float32 [in_features] tensor on x's device")
+    else:
+        out = moment
+    x2 = x.reshape(-1, K).contiguous()
+    if x2.shape[0] == 0:
+        return out.zero_() if moment is None else out
+    with _on_device(x.device):
+        _lib.check(_lib.load().mxq_col_moment(x2.data_ptr(), _TORCH2CODE[x.dtype], x2.shape[0], K,
+                                              moment.data_ptr() if moment is not None else None, out.data_ptr(), _stream(x2)),
+                   "mxq_col_moment")
+    return out
+
+
+def quant_error(W: torch.Tensor, p, col_weight: Optional[torch.Tensor] = None, with_ref: bool = False):
+    """err_rows fp32 [N]: err_rows[n] = sum_k c[k] (W[n, k] - W'[n, k])^2, W' the fp16 weight ``dequant(p)`` would write, c =
+    ``col_weight`` (fp32 [K]; None: ones) -- with c = E[x_k^2] (``col_moment`` / tokens) the diagonal-Hessian estimate of the
+    squared output error of the Linear, row by row.  ``with_ref``: also ref_rows[n] = sum_k c[k] W[n, k]^2, returned as
+    (err_rows, ref_rows).  One fused kernel (include/mxq_hip.h: mxq_quant_error): W' is never written to memory.
+    W: fp16 / bf16 / fp32 [N, K] on the GPU, the shape of ``p`` (a PackedMXQ, exact or compact, or a PackedUniform)."""
+    if not isinstance(p, (PackedMXQ, PackedUniform)):
+        raise ValueError("quant_error needs a PackedMXQ or PackedUniform weight")
+    _need_gpu(W, p.qweight, col_weight)
+    if W.dim() != 2 or W.dtype not in _TORCH2CODE:
+        raise ValueError("weight must be a 2-D fp16 / bf16 / fp32 tensor")
+    if tuple(W.shape) != (p.N, p.K):
+        raise ValueError(f"weight is {tuple(W.shape)}, the packed weight [{p.N}, {p.K}]")
+    if W.device != p.qweight.device:
+        raise ValueError("W and the packed weight live on different devices")
+    if col_weight is not None:
+        if col_weight.dtype != torch.float32 or col_weight.numel() != p.K or col_weight.device != W.device:
+            raise ValueError("col_weight must be a float32 tensor of in_features entries on W's device")
+        col_weight = col_weight.reshape(-1).contiguous()
+    W = W.contiguous()
+    err = torch.empty(p.N, dtype=torch.float32, device=W.device)
+    ref = torch.empty(p.N, dtype=torch.float32, device=W.device) if with_ref else None
+    with _on_device(W.device):
+        _lib.check(_lib.load().mxq_quant_error(W.data_ptr(), _TORCH2CODE[W.dtype], p.qweight.data_ptr(), p.rowmeta.data_ptr(),
+                                               col_weight.data_ptr() if col_weight is not None else None, err.data_ptr(),
+                                               ref.data_ptr() if ref is not None else None, p.N, p.K, _layout_code(p),
+                                               _stream(W)), "mxq_quant_error")
+    return (err, ref) if with_ref else err
