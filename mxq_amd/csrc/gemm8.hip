@@ -13,6 +13,15 @@
 //     range check) -- no VALU work in the loop at all.  (Round 1's kernel put the 2-bit dequant, ~48 VALU ops per
 //     K-step, INSIDE the MFMA waves' instruction streams: an in-order wave that carries VALU chains between its
 //     MFMAs stalls its MFMAs on them, and both MFMA waves of a SIMD do so in lockstep.)
+//     The two MFMA waves of a SIMD (w and w + 4) do NOT run the same program in the 256-token builds: waves 0-3 run the
+//     LEADING K-step (mma_step: 16 MFMAs' worth of fragments carried across the barrier), waves 4-7 the LAGGING one
+//     (mma_step_lag: the same reads, DMA issues, wait and barrier, but all 32 MFMAs a whole step behind their reads, each
+//     register group reloaded in place behind its last MFMA -- no extra VGPR) at a static s_setprio 1.  In phase, both
+//     waves reached their read bursts, their DMA issues and the barrier together; the younger one lost every
+//     arbitration and its 1270-1300-cycle chain set the step while the older one sat 730-750 cycles at the barrier.
+//     Staggered and prioritised, the lagging wave has register-resident MFMAs whenever the leading one reads or
+//     waits: 1616 -> 1574 stamped cycles per step, +1.1 % on the headline (profiles/gemm8_stagger_ab.txt; either half
+//     alone gains nothing).  Results are bit-identical: every accumulator still sums in ascending k.
 //   * waves 8-11 "dequant waves" (one per SIMD): the whole dequant (2-bit LUT / v_perm groups and the 4-bit arm)
 //     into the fp16 W16 tile.  The packed words come straight from global memory into registers (6-7 dword loads
 //     per thread and chunk through the tile's buffer descriptor), a GROUP of 3 chunks at a time; a burst converts the
@@ -192,6 +201,20 @@ constexpr int SK_STAMP_OFF = 32768;   // bytes: the stamps' area in the workspac
 // parked pieces and every wait gives up after 4096 polls -- the launch must end with the workspace's status words set and
 // the starved tiles poisoned, not with silently wrong sums
 [[maybe_unused]] constexpr int EXP_SK_WITHHOLD = 65536;
+// the two MFMA waves of a SIMD (w and w + 4; builds with N_MMA == 8 only; correct, bit-identical results):
+// 131072 = waves 4-7 run the lagging K-step (mma_step_lag: their MFMAs one step behind the leading waves');
+// 262144 = waves 4-7 at a static s_setprio 1 (below the dequant waves' 3), no per-step flips
+[[maybe_unused]] constexpr int EXP_STAGGER = 131072, EXP_LAG_PRIO = 262144;
+// 524288 = without what the product ships of the two (MXQ_G8_STAGGER / MXQ_G8_LAG_PRIO: what ABL = 0 runs), so that the four
+// arms are 524288 (in phase), + 131072 (stagger), + 262144 (priority), + 393216 (both) whatever ships
+[[maybe_unused]] constexpr int EXP_INPHASE = 524288;
+// what ships (= what ABL 0 runs in the builds with two MFMA waves per SIMD): both
+#ifndef MXQ_G8_STAGGER
+#define MXQ_G8_STAGGER 1
+#endif
+#ifndef MXQ_G8_LAG_PRIO
+#define MXQ_G8_LAG_PRIO 1
+#endif
 
 // XCD-aware tile order (speed only): tiles are dealt to the 8 XCDs as compact 2-D blocks (4 x 2 regions)
 __device__ __forceinline__ void tile_of_block(int bid, int tiles_m, int tiles_n, int& tm, int& tn) {
@@ -262,6 +285,19 @@ __device__ __forceinline__ void load_frags(const char* smem, int t, int kk, int 
 #pragma unroll
     for (int j = 0; j < NJ; ++j) xf[j] = *(const half8*)(a_base + swz(wm * (16 * NJ) + j * 16 + fr, kk * 4 + fq));
 }
+// the same reads one register group at a time (the lagging waves reload a fragment as soon as its last MFMA has issued)
+template <bool DENSE, int I0, int I1>
+__device__ __forceinline__ void load_w(const char* smem, int t, int kk, int wn, int fr, int fq, Frag4& wf) {
+    const char* w_base = DENSE ? smem + OFF_WD + (t % WD_SLOTS) * W_STAGE : smem + OFF_W + (t & 1) * W_STAGE;
+#pragma unroll
+    for (int i = I0; i < I1; ++i) wf[i] = *(const half8*)(w_base + swz(wn * 64 + i * 16 + fr, kk * 4 + fq));
+}
+template <int J0, int J1>
+__device__ __forceinline__ void load_x(const char* smem, int t, int kk, int wm, int fr, int fq, FragX& xf) {
+    const char* a_base = smem + OFF_A + (t % A_SLOTS) * A_STAGE;
+#pragma unroll
+    for (int j = J0; j < J1; ++j) xf[j] = *(const half8*)(a_base + swz(wm * (16 * NJ) + j * 16 + fr, kk * 4 + fq));
+}
 
 // ABL_FILL (profiling builds): FILLN independent v_add_f32 behind every MFMA, pinned there by sched_group_barrier -- what
 // vector-ALU work costs when it sits IN the MFMA waves' own streams, one or two ops per MFMA gap (r04 probe)
@@ -287,6 +323,13 @@ __device__ __forceinline__ void mfma_rows(AccT& acc, const Frag4& wf, const Frag
             __builtin_amdgcn_sched_group_barrier(0x002, FILLN, 0);   // FILLN VALU ops
         }
     }
+}
+
+// the one MFMA (row 3, token block J) of mfma_rows<3, 4>
+template <int J, int ABL>
+__device__ __forceinline__ void mfma_at(AccT& acc, const Frag4& wf, const FragX& xf) {
+    if constexpr (ABL & ABL_NO_MFMA) asm volatile("" ::"v"(wf[3]), "v"(xf[J]));
+    else acc[3][J] = mfma16x32<G8_BF16>(wf[3], xf[J], acc[3][J]);
 }
 
 // the x tile of K-step t: wave w fills rows 32w .. 32w+31 of slot t % 3 with 4 DMAs of 8 full 128-B rows;
@@ -381,6 +424,79 @@ __device__ __forceinline__ void mma_step(char* smem, int t, int wave, int wm, in
     if constexpr (((ABL >> 6) & 3) != 0) asm volatile("" ::"v"(fl.f[0]), "v"(fl.f[1]), "v"(fl.f[2]), "v"(fl.f[3]));
     if constexpr (MXQ_STAMPS(ABL)) t1 = stamp();
     // this step's 4 DMAs stay in flight across the barrier; the previous step's (x of step t+1) have landed
+    if constexpr (ISSUE && (ABL & ABL_HALF_XDMA) != 0) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
+    else if constexpr (ISSUE && !(ABL & ABL_NO_XDMA)) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    if constexpr (MXQ_STAMPS(ABL)) t2 = stamp();
+    __builtin_amdgcn_s_barrier();
+    if constexpr (MXQ_STAMPS(ABL)) {
+        const u64t t3 = stamp();
+        st.work += t1 - t0; st.wait += t2 - t1; st.bar += t3 - t2; st.n += 1;
+    }
+}
+
+template <int ABL>
+constexpr bool g8_stagger() { return N_MMA == 8 && ((ABL & EXP_STAGGER) || (MXQ_G8_STAGGER && !(ABL & EXP_INPHASE))); }
+template <int ABL>
+constexpr bool g8_lag_prio() { return N_MMA == 8 && ((ABL & EXP_LAG_PRIO) || (MXQ_G8_LAG_PRIO && !(ABL & EXP_INPHASE))); }
+
+// The same K-step t >= 1 for the LAGGING waves (w >= N_MMA / 2, the second MFMA wave of each SIMD; EXP_STAGGER): the reads
+// of step t, the x DMAs of step t+2 and the counted wait stand where mma_step has them relative to the barriers -- every
+// fragment of step t is in registers before barrier t, so the ring slots live exactly as long -- but the MFMAs are ALL
+// of step t-1: both fragment sets cross the barrier unmultiplied (32 MFMAs carried instead of 16), and each register group
+// is reloaded with step t's fragment as soon as its last MFMA has issued (no second copy: zero extra VGPRs).  While the
+// leading wave of the SIMD sits in a read burst, in its wait or at the barrier, this one still has register-resident
+// MFMAs to issue.  An accumulator receives its products in the same ascending-k order: bit-identical sums.
+template <int ABL, bool ISSUE, bool DENSE>
+__device__ __forceinline__ void mma_step_lag(char* smem, int t, int wave, int wm, int wn, int fr, int fq, const XDma& xd,
+                                             AccT& acc, Frag4& wf0, FragX& xf0, Frag4& wf1, FragX& xf1, Stamps& st) {
+    constexpr int A = ABL & ~192;   // (the in-stream filler probe is the leading waves')
+    u64t t0 = 0, t1 = 0, t2 = 0;
+    if constexpr (MXQ_STAMPS(ABL)) t0 = stamp();
+    mfma_rows<0, 2, A>(acc, wf0, xf0);                       // (t-1, kk=0)
+    MXQ_FENCE();
+    load_w<DENSE, 0, 2>(smem, t, 0, wn, fr, fq, wf0);
+    MXQ_FENCE();
+    mfma_rows<2, 3, A>(acc, wf0, xf0);
+    MXQ_FENCE();
+    load_w<DENSE, 2, 3>(smem, t, 0, wn, fr, fq, wf0);
+    if constexpr (ISSUE && !(ABL & ABL_NO_XDMA)) issue_x<0, 2>(xd, smem, wave, t + 2);
+    MXQ_FENCE();
+    mfma_rows<3, 4, A>(acc, wf0, xf0);
+    MXQ_FENCE();
+    load_w<DENSE, 3, 4>(smem, t, 0, wn, fr, fq, wf0);
+    load_x<0, NJ>(smem, t, 0, wm, fr, fq, xf0);
+    MXQ_FENCE();
+    mfma_rows<0, 2, A>(acc, wf1, xf1);                       // (t-1, kk=1)
+    MXQ_FENCE();
+    load_w<DENSE, 0, 2>(smem, t, 1, wn, fr, fq, wf1);
+    if constexpr (ISSUE && !(ABL & (ABL_NO_XDMA | ABL_HALF_XDMA))) issue_x<2, 4>(xd, smem, wave, t + 2);
+    MXQ_FENCE();
+    mfma_rows<2, 3, A>(acc, wf1, xf1);
+    MXQ_FENCE();
+    load_w<DENSE, 2, 3>(smem, t, 1, wn, fr, fq, wf1);
+    MXQ_FENCE();
+    // the last row token block by token block: x fragment j is free once MFMA (3, j) has issued
+    static_assert(NJ == 4 || N_MMA != 8, "the lagging K-step is written for 64 x 64 sub-tiles");
+    if constexpr (NJ == 4) {
+        mfma_at<0, A>(acc, wf1, xf1);
+        MXQ_FENCE();
+        load_x<0, 1>(smem, t, 1, wm, fr, fq, xf1);
+        MXQ_FENCE();
+        mfma_at<1, A>(acc, wf1, xf1);
+        MXQ_FENCE();
+        load_x<1, 2>(smem, t, 1, wm, fr, fq, xf1);
+        MXQ_FENCE();
+        mfma_at<2, A>(acc, wf1, xf1);
+        MXQ_FENCE();
+        load_x<2, 3>(smem, t, 1, wm, fr, fq, xf1);
+        MXQ_FENCE();
+        mfma_at<3, A>(acc, wf1, xf1);
+        MXQ_FENCE();
+        load_x<3, 4>(smem, t, 1, wm, fr, fq, xf1);
+        load_w<DENSE, 3, 4>(smem, t, 1, wn, fr, fq, wf1);
+    }
+    if constexpr (MXQ_STAMPS(ABL)) t1 = stamp();
     if constexpr (ISSUE && (ABL & ABL_HALF_XDMA) != 0) asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
     else if constexpr (ISSUE && !(ABL & ABL_NO_XDMA)) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -673,10 +789,13 @@ __device__ __forceinline__ void sk_finish_owner(const SkSeg& sk, int own, int NT
 // sit in between, so the first wait is a full one).  After the last barrier, BEFORE the final 16 MFMAs and the
 // output, `next(...)` runs: the persistent loop issues the next tile's prologue DMAs there, which then fly under
 // this tile's epilogue.
-template <int ABL, bool DENSE, class Next>
-__device__ __forceinline__ void mma_segment(char* smem, int wave, int lane, int NT, const XDma& xd, bool pre,
-                                            uint16_t* __restrict__ y, int M, int N, int m0, int n0, int NT_tile,
-                                            SkSeg& sk, Next&& next) {
+// LAG: the segment of a lagging wave (the second MFMA wave of its SIMD, mma_step_lag) -- a template parameter and not a
+// run-time flag, so that each role has its own loops and its own accumulator flow (one body with the flag as a condition
+// around the MFMAs spilled ~1200 registers where the two flows met).
+template <int ABL, bool DENSE, bool LAG, class Next>
+__device__ __forceinline__ void mma_segment_role(char* smem, int wave, int lane, int NT, const XDma& xd, bool pre,
+                                                 uint16_t* __restrict__ y, int M, int N, int m0, int n0, int NT_tile,
+                                                 SkSeg& sk, Next&& next) {
     const int wm = wave / WGN, wn = wave % WGN, fr = lane & 15, fq = lane >> 4;
     AccT acc;
 #pragma unroll
@@ -695,15 +814,15 @@ __device__ __forceinline__ void mma_segment(char* smem, int wave, int lane, int 
     __builtin_amdgcn_s_barrier();   // prologue barrier 1: x tile 0 and packed blocks 0..3 landed
     __builtin_amdgcn_s_barrier();   // prologue barrier 2: W16(0) written by the dequant waves
 
-    // step 0: no previous half
+    // step 0: no previous half (a lagging wave loads both fragment sets and multiplies nothing yet)
     load_frags<DENSE>(smem, 0, 0, wm, wn, fr, fq, wf0, xf0);
     load_frags<DENSE>(smem, 0, 1, wm, wn, fr, fq, wf1, xf1);
     if (NT > 2) {
         if constexpr (!(ABL & ABL_NO_XDMA)) issue_x<0, 4>(xd, smem, wave, 2);
-        mfma_rows<0, 4, ABL & ~192>(acc, wf0, xf0);
+        if constexpr (!LAG) mfma_rows<0, 4, ABL & ~192>(acc, wf0, xf0);
         asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
     } else {
-        mfma_rows<0, 4, ABL & ~192>(acc, wf0, xf0);
+        if constexpr (!LAG) mfma_rows<0, 4, ABL & ~192>(acc, wf0, xf0);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     }
     __builtin_amdgcn_s_barrier();
@@ -712,7 +831,11 @@ __device__ __forceinline__ void mma_segment(char* smem, int wave, int lane, int 
     Stamps st = {0, 0, 0, 0};
     u64t rt0 = 0;
     if constexpr (MXQ_STAMPS(ABL)) asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt0)::"memory");
-    for (; t + 2 < NT; ++t) mma_step<ABL, true, DENSE>(smem, t, wave, wm, wn, fr, fq, xd, acc, wf0, xf0, wf1, xf1, st);
+    if constexpr (LAG) {
+        for (; t + 2 < NT; ++t) mma_step_lag<ABL, true, DENSE>(smem, t, wave, wm, wn, fr, fq, xd, acc, wf0, xf0, wf1, xf1, st);
+    } else {
+        for (; t + 2 < NT; ++t) mma_step<ABL, true, DENSE>(smem, t, wave, wm, wn, fr, fq, xd, acc, wf0, xf0, wf1, xf1, st);
+    }
     if constexpr (MXQ_STAMPS(ABL)) {   // this workgroup's wave: {work, wait, barrier, steps} cycle sums
         u64t rt1;                              // + the same span on the constant 100 MHz clock (high half of word 3): the core clock held
         asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt1)::"memory");
@@ -721,8 +844,13 @@ __device__ __forceinline__ void mma_segment(char* smem, int wave, int lane, int 
             d[0] = st.work; d[1] = st.wait; d[2] = st.bar; d[3] = st.n | ((rt1 - rt0) << 32);
         }
     }
-    for (; t < NT; ++t) mma_step<ABL, false, DENSE>(smem, t, wave, wm, wn, fr, fq, xd, acc, wf0, xf0, wf1, xf1, st);
-    next();                                  // the ring is idle from here on
+    if constexpr (LAG) {
+        for (; t < NT; ++t) mma_step_lag<ABL, false, DENSE>(smem, t, wave, wm, wn, fr, fq, xd, acc, wf0, xf0, wf1, xf1, st);
+    } else {
+        for (; t < NT; ++t) mma_step<ABL, false, DENSE>(smem, t, wave, wm, wn, fr, fq, xd, acc, wf0, xf0, wf1, xf1, st);
+    }
+    next();                                  // the ring is idle from here on: a lagging wave's reads lie before the barrier too
+    if constexpr (LAG) mfma_rows<0, 4, ABL & ~192>(acc, wf0, xf0);   // a lagging wave's backlog is the whole last step: (NT-1, kk=0) first
     mfma_rows<0, 4, ABL & ~192>(acc, wf1, xf1);     // (NT-1, kk=1)
     // (three ways out from here -- store, park, owner's reduction: without this pin the register allocator renames the
     //  accumulators across the last 16 MFMAs to suit one of them and spills 28 registers)
@@ -758,6 +886,21 @@ __device__ __forceinline__ void mma_segment(char* smem, int wave, int lane, int 
             for (int j = 0; j < NJ; ++j) s_ += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
         if (s_ == 123.456f) y[0] = 1;
     }
+}
+
+// Waves w and w + N_MMA / 2 share a SIMD.  With the stagger the second of them runs the lagging segment: chosen by wave
+// number (>= N_MMA / 2), never by parity -- odd / even waves sit on different SIMDs.
+template <int ABL, bool DENSE, class Next>
+__device__ __forceinline__ void mma_segment(char* smem, int wave, int lane, int NT, const XDma& xd, bool pre,
+                                            uint16_t* __restrict__ y, int M, int N, int m0, int n0, int NT_tile,
+                                            SkSeg& sk, Next&& next) {
+    if constexpr (g8_stagger<ABL>()) {
+        if (wave >= N_MMA / 2) {
+            mma_segment_role<ABL, DENSE, true>(smem, wave, lane, NT, xd, pre, y, M, N, m0, n0, NT_tile, sk, next);
+            return;
+        }
+    }
+    mma_segment_role<ABL, DENSE, false>(smem, wave, lane, NT, xd, pre, y, M, N, m0, n0, NT_tile, sk, next);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1408,6 +1551,12 @@ __global__ __launch_bounds__(THREADS) void G8_KERNEL(const uint16_t* __restrict_
     auto nothing = [] {};
     if (wave < N_MMA) {
         if constexpr ((ABL & EXP_MMA_PRIO) != 0) __builtin_amdgcn_s_setprio(3);   // experiment: MFMA waves first
+        // the second-dispatched MFMA wave of each SIMD loses every arbitration by age; one static priority for that half
+        // (never flipped per step), still below the dequant waves' 3, makes the LAGGING waves the ones served first: alone
+        // it only swaps the two waves' timings, with the stagger it is what turns the lag into time (header)
+        if constexpr (g8_lag_prio<ABL>()) {
+            if (wave >= N_MMA / 2) __builtin_amdgcn_s_setprio(1);
+        }
     } else {
         // the dequant chain is the longer one of a K-step: its VALU ops go first whenever they are ready (the MFMAs
         // lose a 4-cycle issue slot each time, the chain would lose up to 16).  Not in the 128-token build, whose eight
@@ -1838,6 +1987,15 @@ extern "C" int G8_SYM(prof_, _ablate_f16)(const void* x, const void* qweight, co
         case 68: return launch8<68>(x, qweight, rowmeta, y, M, N, K, nullptr, 0, false, stream);
         case 132: return launch8<132>(x, qweight, rowmeta, y, M, N, K, nullptr, 0, false, stream);
         case 196: return launch8<196>(x, qweight, rowmeta, y, M, N, K, nullptr, 0, false, stream);
+#if MXQ_G8_BM == 256
+        // the SIMD partners' arms (correct results): in phase, lagging K-step for waves 4-7, static priority for them, both
+        case EXP_INPHASE: return launch8<EXP_INPHASE>(x, qweight, rowmeta, y, M, N, K, nullptr, 0, false, stream);
+        case EXP_INPHASE | EXP_STAGGER: return launch8<EXP_INPHASE | EXP_STAGGER>(x, qweight, rowmeta, y, M, N, K, nullptr, 0, false, stream);
+        case EXP_INPHASE | EXP_LAG_PRIO: return launch8<EXP_INPHASE | EXP_LAG_PRIO>(x, qweight, rowmeta, y, M, N, K, nullptr, 0, false, stream);
+        case EXP_INPHASE | EXP_STAGGER | EXP_LAG_PRIO: return launch8<EXP_INPHASE | EXP_STAGGER | EXP_LAG_PRIO>(x, qweight, rowmeta, y, M, N, K, nullptr, 0, false, stream);
+        case EXP_INPHASE | ABL_NO_DEQ: return launch8<EXP_INPHASE | ABL_NO_DEQ>(x, qweight, rowmeta, y, M, N, K, nullptr, 0, false, stream);
+        case EXP_INPHASE | EXP_STAGGER | ABL_NO_DEQ: return launch8<EXP_INPHASE | EXP_STAGGER | ABL_NO_DEQ>(x, qweight, rowmeta, y, M, N, K, nullptr, 0, false, stream);
+#endif
     }
     return MXQ_E_SHAPE;   // not an ablation this build carries
 }
@@ -1893,6 +2051,12 @@ extern "C" int G8_SYM(prof_, _stamps_f16)(const void* x, const void* qweight, co
         case 1024: return launch8_stamps<4096 + 1024>(x, qweight, rowmeta, y, M, N, K, dbg, stream);
         case 4: return launch8_stamps<4096 + 4>(x, qweight, rowmeta, y, M, N, K, dbg, stream);
         case 2: return launch8_stamps<4096 + 2>(x, qweight, rowmeta, y, M, N, K, dbg, stream);
+#if MXQ_G8_BM == 256
+        case EXP_INPHASE: return launch8_stamps<4096 + (EXP_INPHASE)>(x, qweight, rowmeta, y, M, N, K, dbg, stream);
+        case EXP_INPHASE | EXP_STAGGER: return launch8_stamps<4096 + (EXP_INPHASE | EXP_STAGGER)>(x, qweight, rowmeta, y, M, N, K, dbg, stream);
+        case EXP_INPHASE | EXP_LAG_PRIO: return launch8_stamps<4096 + (EXP_INPHASE | EXP_LAG_PRIO)>(x, qweight, rowmeta, y, M, N, K, dbg, stream);
+        case EXP_INPHASE | EXP_STAGGER | EXP_LAG_PRIO: return launch8_stamps<4096 + (EXP_INPHASE | EXP_STAGGER | EXP_LAG_PRIO)>(x, qweight, rowmeta, y, M, N, K, dbg, stream);
+#endif
     }
     return MXQ_E_SHAPE;
 }

@@ -3,7 +3,9 @@
 stamps in libmxq_hip_prof.so; the stamps perturb the run: read the SHARES, not the length).  The dequant waves'
 stamps went away with their per-step structure (they now work in bursts of three chunks); their rows in
 profiles/r02_*stamps* are from the per-step kernel earlier in round 2.
-    python tools/gemm_stamps.py [--m 2048] [--n 4096] [--k 4096] [--abl 0,2048,4,2]"""
+    python tools/gemm_stamps.py [--m 2048] [--n 4096] [--k 4096] [--abl 0,2048,4,2]
+The two MFMA waves of a SIMD in phase / waves 4-7 lagging / waves 4-7 prioritised / both (csrc/gemm8.hip, EXP_INPHASE +
+EXP_STAGGER + EXP_LAG_PRIO): --per-wave --abl 524288,655360,786432,917504 (tools/ab_gemm.py: abl8:524288, ...)."""
 import argparse
 import ctypes
 import os
