@@ -489,6 +489,34 @@ size_t mxq_attn_split_workspace_bytes(int heads, int splits);
 int mxq_attn_decode_split_f16(const void* qkv, void* k_cache, void* v_cache, const void* pos, const void* rope_row, void* out,
                               int heads, int head_dim, int max_ctx, int splits, void* workspace, void* stream);
 
+/* Prompt prefill for the same caches (csrc/attn_prefill.hip; no reference counterpart): rotary embedding, KV-cache append and
+ * causal attention for `tokens` tokens at once; token t sits at position pos0 + t.  qkv fp16 [tokens, 3*heads*128] row-major
+ * (the fused q|k|v Linear's output); caches fp16 [heads][max_ctx][128] as above; cos/sin f32 [max_ctx][64]; out fp16
+ * [tokens, heads*128].  pos0 is a HOST int (the caller mirrors the position: mxq_amd/llama_decode.py's ContextWindow), so an
+ * invalid position is refused here with MXQ_E_SHAPE and there is no NaN-poison path.
+ * mxq_kv_append_rope_f16 (one launch): for every (t, head) the rotated key and the value go into cache row pos0 + t.  The
+ * rotation is the decode entries' -- fp32 products, one fp32 add / subtract, a single fp16 rounding -- and the appended rows are
+ * BIT-IDENTICAL to the rows mxq_attn_decode_row_f16 appends for the same qkv row and position.
+ * mxq_attn_prefill_f16 (two launches, stream order the only synchronisation): the append above, then causal flash attention
+ * on v_mfma_f32_16x16x32_f16, one workgroup per (head, 64 queries), keys and values read from the cache ONLY (rows [0, pos0 + t]
+ * for query t: a chunked prefill, pos0 > 0, needs nothing extra).  Rounding points: q rotated in fp32 and rounded once to fp16
+ * (the decode kernels' q16); scores q16 . k with fp32 accumulation, times rsqrtf(128) in fp32, NOT rounded to fp16 (as the
+ * split decode kernel beyond 128 keys); an online softmax over 64-key tiles with the running maximum and row sum in fp32 and
+ * __expf; each probability rounded once to fp16 as the P.V operand, while the row sum adds the fp32 value BEFORE that
+ * rounding; O accumulated in fp32, divided by the fp32 row sum and rounded once to fp16.  The mask is a select.
+ * Cache rows at and beyond pos0 + tokens may hold anything, NaN included: they are neither read into any result nor written
+ * (only the append writes to the caches, rows pos0 .. pos0 + tokens - 1; the attention launch writes `out` only).
+ * qkv and the cache rows below pos0 must be finite: a masked key enters P.V as 0 times its value, so an Inf or NaN in the value
+ * of a LATER token of the same 64-query block turns the earlier queries of that block NaN (0 * Inf), which the
+ * token-by-token entries would not.
+ * Validation, before anything is launched: MXQ_E_NULL; MXQ_E_SHAPE for tokens <= 0, heads <= 0, head_dim != 128, max_ctx <= 0
+ * or > 32768, pos0 < 0, pos0 + tokens > max_ctx; MXQ_E_ALIGN: qkv, both caches and out 16 bytes, the tables 4.  No
+ * workspace, no allocation, no synchronisation; results are deterministic (no atomics). */
+int mxq_kv_append_rope_f16(const void* qkv, void* k_cache, void* v_cache, const void* cos_t, const void* sin_t,
+                           int tokens, int pos0, int heads, int head_dim, int max_ctx, void* stream);
+int mxq_attn_prefill_f16(const void* qkv, void* k_cache, void* v_cache, const void* cos_t, const void* sin_t, void* out,
+                         int tokens, int pos0, int heads, int head_dim, int max_ctx, void* stream);
+
 /* Decode-harness glue (BASELINE config 3), not part of the reference's hot path: final RMSNorm + the fp16 lm_head
  * Linear + greedy argmax of ONE token.  h fp16[K], norm_w fp16[K], w fp16[V, K] (row-major nn.Linear weight), K = 4096;
  * the normalised row is fp16(h * rsqrt(mean h^2 + eps)) * norm_w, a logit the fp32 dot rounded to fp16, the result

@@ -93,6 +93,8 @@ SIGNATURES = {
     "mxq_lmhead_argmax_advance_f16": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                               c_void_p, c_int, c_void_p]),
     "mxq_attn_decode_row_f16": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_void_p]),
+    "mxq_kv_append_rope_f16": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p]),
+    "mxq_attn_prefill_f16": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
     "mxq_fakequant_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "mxq_fakequant_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_int, c_void_p]),
     "mxq_gemv_awq_f16": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_void_p]),

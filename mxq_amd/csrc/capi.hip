@@ -226,6 +226,32 @@ int mxq_attn_decode_row_f16(const void* qkv, void* k_cache, void* v_cache, const
                                       head_dim, max_ctx, 1, (hipStream_t)stream);
 }
 
+// prompt prefill (csrc/attn_prefill.hip): the two entries share one validation, before anything is launched
+static int attn_prefill_check(const void* qkv, const void* k_cache, const void* v_cache, const void* cos_t, const void* sin_t,
+                              const void* out, bool with_out, int tokens, int pos0, int heads, int head_dim, int max_ctx) {
+    if (!qkv || !k_cache || !v_cache || !cos_t || !sin_t || (with_out && !out)) return MXQ_E_NULL;
+    if (tokens <= 0 || heads <= 0 || head_dim != 128 || max_ctx <= 0 || max_ctx > 32768 || pos0 < 0 || pos0 > max_ctx - tokens)
+        return MXQ_E_SHAPE;
+    if (!aligned16(qkv) || !aligned16(k_cache) || !aligned16(v_cache) || (with_out && !aligned16(out)) || !aligned4(cos_t) ||
+        !aligned4(sin_t))
+        return MXQ_E_ALIGN;
+    return 0;
+}
+
+int mxq_kv_append_rope_f16(const void* qkv, void* k_cache, void* v_cache, const void* cos_t, const void* sin_t, int tokens, int pos0,
+                           int heads, int head_dim, int max_ctx, void* stream) {
+    if (int e = attn_prefill_check(qkv, k_cache, v_cache, cos_t, sin_t, nullptr, false, tokens, pos0, heads, head_dim, max_ctx)) return e;
+    return mxq_launch_kv_append_rope_f16(qkv, k_cache, v_cache, cos_t, sin_t, tokens, pos0, heads, max_ctx, (hipStream_t)stream);
+}
+
+int mxq_attn_prefill_f16(const void* qkv, void* k_cache, void* v_cache, const void* cos_t, const void* sin_t, void* out, int tokens,
+                         int pos0, int heads, int head_dim, int max_ctx, void* stream) {
+    if (int e = attn_prefill_check(qkv, k_cache, v_cache, cos_t, sin_t, out, true, tokens, pos0, heads, head_dim, max_ctx)) return e;
+    if (int e = mxq_launch_kv_append_rope_f16(qkv, k_cache, v_cache, cos_t, sin_t, tokens, pos0, heads, max_ctx, (hipStream_t)stream))
+        return e;
+    return mxq_launch_attn_prefill_f16(qkv, k_cache, v_cache, cos_t, sin_t, out, tokens, pos0, heads, max_ctx, (hipStream_t)stream);
+}
+
 int mxq_lmhead_argmax_f16(const void* h, const void* norm_w, float eps, const void* w, int V, int K, void* part,
                           int part_slots, void* token, void* stream) {
     if (!h || !norm_w || !w || !part || !token) return MXQ_E_NULL;

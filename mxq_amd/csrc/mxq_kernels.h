@@ -192,6 +192,11 @@ int mxq_launch_attn_decode_split_f16(const void* qkv, void* k_cache, void* v_cac
                                      void* out, int heads, int head_dim, int max_ctx, int splits, void* ws, hipStream_t stream);
 int mxq_launch_rope_row_f32(const void* pos, const void* cos_t, const void* sin_t, void* row, int half_dim, int max_ctx,
                             const void* tok, const void* embed, int vocab, int hidden, void* h_out, hipStream_t stream);
+// csrc/attn_prefill.hip: rope + KV append for `tokens` rows at pos0 .. (launch A), causal MFMA attention over the cache (launch B)
+int mxq_launch_kv_append_rope_f16(const void* qkv, void* k_cache, void* v_cache, const void* cos_t, const void* sin_t, int tokens,
+                                  int pos0, int heads, int max_ctx, hipStream_t stream);
+int mxq_launch_attn_prefill_f16(const void* qkv, const void* k_cache, const void* v_cache, const void* cos_t, const void* sin_t,
+                                void* out, int tokens, int pos0, int heads, int max_ctx, hipStream_t stream);
 int mxq_launch_fakequant_fwd(const void* w, void* out, int rows, int cols, int num_bits, int dtype,
                              hipStream_t stream);
 int mxq_launch_fakequant_bwd(const void* grad_out, const void* w, void* grad_in, int64_t n, float lo, float hi,

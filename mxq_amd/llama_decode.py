@@ -242,6 +242,58 @@ class DecodeStage:
         self.window.take(1)
         self.pos += 1
 
+    # -- prompt prefill --------------------------------------------------------------------------------
+    def prefill(self, h):
+        """A prompt of T tokens through this stage's layers in one pass.  h [T, hidden] fp16 -> [T, hidden]; the KV caches
+        hold the prompt's rows afterwards and both positions have moved on by T, so ``step`` / the captured graphs continue
+        at position T.  Per layer the unfused branch of ``step`` at T rows -- RMSNorm, q|k|v through ``packing.linear``'s own
+        dispatch (the prefill GEMM at prompt lengths), mxq_attn_prefill_f16 (RoPE + cache append + causal MFMA attention,
+        csrc/attn_prefill.hip), o_proj + skip, RMSNorm, gate|up, SiLU * up, down_proj + skip.  Eager only; head dim 128 only
+        (there is no torch attention fallback).  Raises RuntimeError, before any launch and with nothing changed, when the
+        prompt does not fit the cache; a failure in a later launch leaves both positions where they were."""
+        if self.hd != 128:
+            raise ValueError(f"prefill needs head dim 128 (csrc/attn_prefill.hip), this stage has {self.hd}")
+        if h.dim() != 2 or h.shape[1] != self.hidden or h.dtype != torch.float16:
+            raise ValueError(f"prefill takes fp16 [T, {self.hidden}], got {h.dtype} {tuple(h.shape)}")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("prefill is eager only: the position is a host argument of its attention launch")
+        T = h.shape[0]
+        if T == 0:
+            return h.new_empty((0, self.hidden))
+        p0 = self.window.take(T)
+        lib = _lib.load()
+        st = torch.cuda.current_stream(self.dev).cuda_stream
+        try:
+            for i, (qkv, o, gu, down) in enumerate(self.w):
+                y = packing.linear(self._rms(h), qkv).contiguous()
+                a = torch.empty((T, self.hidden), dtype=torch.float16, device=self.dev)
+                _lib.check(lib.mxq_attn_prefill_f16(y.data_ptr(), self.k_cache[i].data_ptr(), self.v_cache[i].data_ptr(),
+                                                    self.cos.data_ptr(), self.sin.data_ptr(), a.data_ptr(), T, p0, self.heads,
+                                                    self.hd, self.max_ctx, st), "mxq_attn_prefill_f16")
+                h = h + packing.linear(a, o)
+                gu_y = packing.linear(self._rms(h), gu)
+                act = torch.nn.functional.silu(gu_y[:, : self.inter].float()).half() * gu_y[:, self.inter:]
+                h = h + packing.linear(act, down)
+        except BaseException:
+            self.window.pos = p0               # nothing advanced the device position: the host mirror goes back with it (the
+            raise                              # cache rows from p0 on may be partly written; they are beyond the position)
+        self.pos += T
+        return h
+
+    def prefill_tokens(self, ids):
+        """Prompt ids (int64 [T], T >= 1) -> the first generated token id (tensor [1]): embedding, ``prefill``, ``head`` on
+        the last row.  Only for a stage that is both first and last.  With the captured token loop the order is
+        ``capture_token_loop(buf)`` -> ``reset()`` -> ``first = prefill_tokens(prompt)`` -> ``decode_tokens(buf, first, n)``:
+        the capture leaves the positions at zero, and the graphs read the device position, so they continue at T."""
+        if getattr(self, "embed", None) is None or getattr(self, "lm_head", None) is None:
+            raise ValueError("prefill_tokens needs the first and the last stage in one process")
+        ids = torch.as_tensor(ids, dtype=torch.int64, device=self.dev).reshape(-1)
+        if ids.numel() == 0:
+            raise ValueError("prefill_tokens needs at least one prompt token")
+        h = self.prefill(self.embed.index_select(0, ids))
+        tok = torch.zeros(1, dtype=torch.int64, device=self.dev)      # (the native head writes the id where it is told to)
+        return self.head(h[-1:], out=tok).reshape(-1)[:1]
+
     # -- hipGraph capture of one stage step --------------------------------------------------------
     def capture(self):
         for _ in range(2):                                            # warm-up outside capture
