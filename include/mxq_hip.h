@@ -489,6 +489,43 @@ size_t mxq_attn_split_workspace_bytes(int heads, int splits);
 int mxq_attn_decode_split_f16(const void* qkv, void* k_cache, void* v_cache, const void* pos, const void* rope_row, void* out,
                               int heads, int head_dim, int max_ctx, int splits, void* workspace, void* stream);
 
+/* BATCHED decode: one token of each of `batch` (1..256) sequences per launch, every sequence ("slot") at its own position.
+ * mxq_attn_decode_batch_f16: qkv fp16 [batch, 3*heads*128]; caches fp16 [batch][heads][max_ctx][128] -- slot b's part is exactly
+ * a cache of the single-sequence and prefill entries above; pos int64 [batch] (device); rope_rows f32 [batch][128], cos | sin
+ * of each slot's OWN position (mxq_embed_rope_rows); out fp16 [batch, heads*128]; splits 1..16.  One launch of heads x splits x
+ * batch workgroups running the device functions of the entries above on each slot's operands, so per slot, by pos[b]:
+ *   0 <= pos[b] < max_ctx and (splits == 1 or pos[b] + 1 <= 128): the out row and the appended K / V row are BIT-IDENTICAL to
+ *     mxq_attn_decode_row_f16 on that slot (fp16 scores, fp16 probabilities: its rounding points);
+ *   0 <= pos[b] < max_ctx otherwise: bit-identical to mxq_attn_decode_split_f16 with the same `splits` (fp16 scores, fp32
+ *     probabilities, the parts merged in fp32 by the slot-and-head's last arriver);
+ *   pos[b] < 0: an EMPTY slot -- nothing of its cache is read into a result or written, its out row is all zero;
+ *   pos[b] >= max_ctx: refused as above -- nothing is written to the cache, the out row is all NaN.
+ * Both special cases are uniform over a workgroup and taken before any barrier; neither touches the workspace.
+ * workspace (nullable when splits == 1): mxq_attn_batch_workspace_bytes(batch, heads, splits) bytes -- one arrival counter per
+ * (slot, head) in the first 1024 * ceil(batch*heads / 256) bytes, zeroed ONCE by the caller and left zeroed by the kernel,
+ * then the {o[128], max, sum} parts per (slot, head, split).  0 for arguments the entry would refuse.
+ * mxq_embed_rope_rows: mxq_embed_rope_row for `batch` slots in one launch of `batch` workgroups: rows f32 [batch][2*half_dim]
+ * = cos | sin of pos[b] clamped into [0, max_ctx) (an empty slot's -1 becomes 0), h_out fp16 [batch, hidden] = embed[tokens[b]]
+ * (int64 [batch], clamped into [0, vocab)); exact copies.  tokens NULL: h_out (and embed, vocab, hidden) unused, untouched.
+ * mxq_rmsnorm_rows_f16: y[r, k] = fp16(fp16(x[r, k] * inv_r) * norm_w[k]), inv_r = rsqrtf(sum_k x[r, k]^2 / K + eps) with
+ * the sum, the division and rsqrtf in fp32: two fp16 roundings per element, as mxq_lmhead_argmax_f16 normalises its row.
+ * x, y fp16 [rows, K], norm_w fp16 [K]; K % 8 == 0; one workgroup per row.
+ * mxq_swiglu_rows_f16: act[r, i] = fp16(fp16(silu(gate)) * up) for gate_up fp16 [rows, 2*inter] = gate | up, silu(g) =
+ * g / (1 + expf(-g)) in fp32 rounded once to fp16, then one fp16 multiply; act fp16 [rows, inter]; inter % 8 == 0.
+ * All are stream-ordered, allocate nothing and read every position from device memory (hipGraph-replayable).
+ * Validation, before anything is launched: MXQ_E_NULL for a NULL operand (workspace and tokens excepted as above);
+ * MXQ_E_SHAPE for batch < 1 or > 256, heads <= 0, head_dim != 128, max_ctx <= 0 or > 32768, splits outside 1..16, splits > 1
+ * without a workspace, rows <= 0, K % 8 != 0, inter % 8 != 0 (and hidden % 8 != 0 with tokens); MXQ_E_ALIGN: caches,
+ * workspace, embed, h_out, x, norm_w, y, gate_up and act 16 bytes; pos and tokens 8; the tables and the rotary rows 4; qkv
+ * and out 2. */
+size_t mxq_attn_batch_workspace_bytes(int batch, int heads, int splits);
+int mxq_attn_decode_batch_f16(const void* qkv, void* k_cache, void* v_cache, const void* pos, const void* rope_rows, void* out,
+                              int batch, int heads, int head_dim, int max_ctx, int splits, void* workspace, void* stream);
+int mxq_embed_rope_rows(const void* tokens, const void* embed, int vocab, int hidden, void* h_out, const void* pos, const void* cos_t,
+                        const void* sin_t, void* rows, int half_dim, int max_ctx, int batch, void* stream);
+int mxq_rmsnorm_rows_f16(const void* x, const void* norm_w, void* y, int rows, int K, float eps, void* stream);
+int mxq_swiglu_rows_f16(const void* gate_up, void* act, int rows, int inter, void* stream);
+
 /* Prompt prefill for the same caches (csrc/attn_prefill.hip; no reference counterpart): rotary embedding, KV-cache append and
  * causal attention for `tokens` tokens at once; token t sits at position pos0 + t.  qkv fp16 [tokens, 3*heads*128] row-major
  * (the fused q|k|v Linear's output); caches fp16 [heads][max_ctx][128] as above; cos/sin f32 [max_ctx][64]; out fp16

@@ -93,6 +93,12 @@ SIGNATURES = {
     "mxq_lmhead_argmax_advance_f16": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                               c_void_p, c_int, c_void_p]),
     "mxq_attn_decode_row_f16": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_void_p]),
+    "mxq_attn_batch_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "mxq_attn_decode_batch_f16": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p, c_void_p]),
+    "mxq_embed_rope_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                    c_int, c_void_p]),
+    "mxq_rmsnorm_rows_f16": (c_int, [c_void_p] * 3 + [c_int, c_int, c_float, c_void_p]),
+    "mxq_swiglu_rows_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "mxq_kv_append_rope_f16": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p]),
     "mxq_attn_prefill_f16": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
     "mxq_fakequant_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

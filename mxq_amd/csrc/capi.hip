@@ -226,6 +226,52 @@ int mxq_attn_decode_row_f16(const void* qkv, void* k_cache, void* v_cache, const
                                       head_dim, max_ctx, 1, (hipStream_t)stream);
 }
 
+// batched decode: `batch` sequences, one token each, every position in device memory (csrc/decode_ops.hip)
+size_t mxq_attn_batch_workspace_bytes(int batch, int heads, int splits) {
+    if (batch < 1 || batch > 256 || heads <= 0 || splits < 1 || splits > 16 || (int64_t)batch * heads > (1 << 20)) return 0;
+    return ::mxq_attn_split_workspace_bytes_impl(batch * heads, splits);
+}
+
+int mxq_attn_decode_batch_f16(const void* qkv, void* k_cache, void* v_cache, const void* pos, const void* rope_rows, void* out,
+                              int batch, int heads, int head_dim, int max_ctx, int splits, void* workspace, void* stream) {
+    if (!qkv || !k_cache || !v_cache || !pos || !rope_rows || !out) return MXQ_E_NULL;
+    if (batch < 1 || batch > 256 || heads <= 0 || (int64_t)batch * heads > (1 << 20) || head_dim != 128 || max_ctx <= 0 ||
+        max_ctx > 32768 || splits < 1 || splits > 16 || (splits > 1 && !workspace))
+        return MXQ_E_SHAPE;
+    if (!aligned16(k_cache) || !aligned16(v_cache) || (workspace && !aligned16(workspace)) || ((uintptr_t)pos & 7) ||
+        !aligned4(rope_rows) || ((uintptr_t)qkv & 1) || ((uintptr_t)out & 1))
+        return MXQ_E_ALIGN;
+    return mxq_launch_attn_decode_batch_f16(qkv, k_cache, v_cache, pos, rope_rows, out, batch, heads, head_dim, max_ctx, splits,
+                                            workspace, (hipStream_t)stream);
+}
+
+int mxq_embed_rope_rows(const void* tokens, const void* embed, int vocab, int hidden, void* h_out, const void* pos, const void* cos_t,
+                        const void* sin_t, void* rows, int half_dim, int max_ctx, int batch, void* stream) {
+    if (!pos || !cos_t || !sin_t || !rows || (tokens && (!embed || !h_out))) return MXQ_E_NULL;
+    if (batch < 1 || batch > 256 || half_dim <= 0 || half_dim > 4096 || max_ctx <= 0 ||
+        (tokens && (vocab <= 0 || hidden <= 0 || hidden % 8 != 0)))
+        return MXQ_E_SHAPE;
+    if ((tokens && (!aligned16(embed) || !aligned16(h_out) || ((uintptr_t)tokens & 7))) || ((uintptr_t)pos & 7) || !aligned4(cos_t) ||
+        !aligned4(sin_t) || !aligned4(rows))
+        return MXQ_E_ALIGN;
+    return mxq_launch_rope_rows_f32(pos, cos_t, sin_t, rows, half_dim, max_ctx, tokens, embed, vocab, hidden, h_out, batch,
+                                    (hipStream_t)stream);
+}
+
+int mxq_rmsnorm_rows_f16(const void* x, const void* norm_w, void* y, int rows, int K, float eps, void* stream) {
+    if (!x || !norm_w || !y) return MXQ_E_NULL;
+    if (rows <= 0 || K <= 0 || K % 8 != 0) return MXQ_E_SHAPE;
+    if (!aligned16(x) || !aligned16(norm_w) || !aligned16(y)) return MXQ_E_ALIGN;
+    return mxq_launch_rmsnorm_rows_f16(x, norm_w, y, rows, K, eps, (hipStream_t)stream);
+}
+
+int mxq_swiglu_rows_f16(const void* gate_up, void* act, int rows, int inter, void* stream) {
+    if (!gate_up || !act) return MXQ_E_NULL;
+    if (rows <= 0 || inter <= 0 || inter % 8 != 0 || (int64_t)rows * ((inter / 8 + 255) / 256) > 0x7FFFFFFF) return MXQ_E_SHAPE;
+    if (!aligned16(gate_up) || !aligned16(act)) return MXQ_E_ALIGN;
+    return mxq_launch_swiglu_rows_f16(gate_up, act, rows, inter, (hipStream_t)stream);
+}
+
 // prompt prefill (csrc/attn_prefill.hip): the two entries share one validation, before anything is launched
 static int attn_prefill_check(const void* qkv, const void* k_cache, const void* v_cache, const void* cos_t, const void* sin_t,
                               const void* out, bool with_out, int tokens, int pos0, int heads, int head_dim, int max_ctx) {

@@ -32,12 +32,15 @@ constexpr int ATT_THREADS = 256;
 // Returns false (before any side effect) when `max_keys` > 0 and the position needs more keys than that: the caller then
 // takes the split path.  (The test sits INSIDE, behind round trip 1: a caller that read the position first and branched
 // would put a dependent round trip in front of every load of this function -- measured +2.2 us per layer.)
+// `neg_fill`: the fp16 bits a NEGATIVE position leaves in the head's output -- NaN for the single-sequence entries (a
+// refusal), zero for the batched entry, where a negative position marks an empty slot (for the same reason it is told
+// apart in here and not by the caller).
 template <bool ROW>
 __device__ __forceinline__ bool attn_one_workgroup(float* sm, int h, const uint16_t* __restrict__ qkv,
                                                    uint16_t* __restrict__ k_cache, uint16_t* __restrict__ v_cache,
                                                    const int64_t* __restrict__ pos_p, const float* __restrict__ cos_t,
                                                    const float* __restrict__ sin_t, uint16_t* __restrict__ out, int heads,
-                                                   int max_ctx, int max_keys = 0) {
+                                                   int max_ctx, int max_keys = 0, uint16_t neg_fill = 0x7E00) {
     float* q_s = sm;                       // q[HD], knew[HD], vnew[HD], scores[max_ctx], red[8], o2[16*HD]
     float* k_s = sm + HD;
     float* v_s = sm + 2 * HD;
@@ -77,7 +80,7 @@ __device__ __forceinline__ bool attn_one_workgroup(float* sm, int h, const uint1
     // so the launcher cannot check it: a position outside the cache must neither be written to the cache nor index
     // the LDS score array.  The head's output is poisoned (NaN) instead, which the caller cannot miss downstream.
     if (pos64 < 0 || pos64 >= max_ctx) {   // uniform over the workgroup: taken before any barrier
-        if (tid < HD) out[h * HD + tid] = 0x7E00;
+        if (tid < HD) out[h * HD + tid] = pos64 < 0 ? neg_fill : (uint16_t)0x7E00;
         return true;
     }
     const int pos = (int)pos64;
@@ -205,20 +208,19 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_kernel(const uint16_t
 // single-workgroup algorithm above bit for bit (the other splits exit at once): short contexts pay nothing.
 // ws: int counters [heads] (zeroed once by the caller; left zeroed), then f32 parts [heads][S][HD + 2] from byte 1024 * ceil(heads / 256).
 constexpr int SPLIT_MIN = 128, SPLIT_CHUNK = 64, MAX_SPLITS = 16;
+// The body of split `split` of head `h` (one workgroup), shared by the single-sequence kernel below and the batched one:
+// `last_s` is the calling kernel's static LDS arrival flag, `neg_fill` as in attn_one_workgroup.
 template <bool ROW>
-__global__ __launch_bounds__(ATT_THREADS) void attn_decode_split_kernel(const uint16_t* __restrict__ qkv,
-                                                                        uint16_t* __restrict__ k_cache,
-                                                                        uint16_t* __restrict__ v_cache,
-                                                                        const int64_t* __restrict__ pos_p,
-                                                                        const float* __restrict__ cos_t,
-                                                                        const float* __restrict__ sin_t,
-                                                                        uint16_t* __restrict__ out, int heads, int max_ctx, int S,
-                                                                        int* __restrict__ cnt, float* __restrict__ part) {
-    extern __shared__ float sm[];
-    const int h = blockIdx.x % heads, split = blockIdx.x / heads;
+__device__ __forceinline__ void attn_split_workgroup(float* sm, int* last_s, int h, int split, const uint16_t* __restrict__ qkv,
+                                                     uint16_t* __restrict__ k_cache, uint16_t* __restrict__ v_cache,
+                                                     const int64_t* __restrict__ pos_p, const float* __restrict__ cos_t,
+                                                     const float* __restrict__ sin_t, uint16_t* __restrict__ out, int heads,
+                                                     int max_ctx, int S, int* __restrict__ cnt, float* __restrict__ part,
+                                                     uint16_t neg_fill = 0x7E00) {
     // split 0 starts as the one-workgroup kernel (all its loads fly with the position's); it comes back unhandled only for a
     // long context.  The other splits have nothing to do for a short or refused position.
-    if (split == 0 && attn_one_workgroup<ROW>(sm, h, qkv, k_cache, v_cache, pos_p, cos_t, sin_t, out, heads, max_ctx, SPLIT_MIN))
+    if (split == 0 &&
+        attn_one_workgroup<ROW>(sm, h, qkv, k_cache, v_cache, pos_p, cos_t, sin_t, out, heads, max_ctx, SPLIT_MIN, neg_fill))
         return;
     const int64_t pos64 = *pos_p;
     if (pos64 < 0 || pos64 >= max_ctx || pos64 + 1 <= SPLIT_MIN) return;
@@ -369,10 +371,9 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_split_kernel(const ui
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    __shared__ int last_s;
-    if (tid == 0) last_s = __hip_atomic_fetch_add(cnt + h, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == S_eff - 1;
+    if (tid == 0) *last_s = __hip_atomic_fetch_add(cnt + h, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == S_eff - 1;
     __syncthreads();
-    if (!last_s) return;
+    if (!*last_s) return;
     // the last arriver of the head: every part was drained before its arrival was counted.  ALL the parts' loads go out
     // together (agent-scope: sc1 buffer loads; clamped to the last part, whose weight is then zero) -- read one after the
     // other, 16 parts were 16 dependent round trips, most of the launch at 2000 keys
@@ -401,13 +402,57 @@ __global__ __launch_bounds__(ATT_THREADS) void attn_decode_split_kernel(const ui
     if (tid == 0) __hip_atomic_store(cnt + h, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+template <bool ROW>
+__global__ __launch_bounds__(ATT_THREADS) void attn_decode_split_kernel(const uint16_t* __restrict__ qkv,
+                                                                        uint16_t* __restrict__ k_cache,
+                                                                        uint16_t* __restrict__ v_cache,
+                                                                        const int64_t* __restrict__ pos_p,
+                                                                        const float* __restrict__ cos_t,
+                                                                        const float* __restrict__ sin_t,
+                                                                        uint16_t* __restrict__ out, int heads, int max_ctx, int S,
+                                                                        int* __restrict__ cnt, float* __restrict__ part) {
+    extern __shared__ float sm[];
+    __shared__ int last_s;
+    attn_split_workgroup<ROW>(sm, &last_s, blockIdx.x % heads, blockIdx.x / heads, qkv, k_cache, v_cache, pos_p, cos_t, sin_t, out,
+                              heads, max_ctx, S, cnt, part);
+}
+
+// BATCHED decode: `batch` sequences in one launch, each with its own caches ([batch][heads][max_ctx][HD]), position, qkv /
+// out row and rotary row; grid = heads x S x batch, block (b * S + split) * heads + h.  A slot's workgroups run exactly
+// the single-sequence bodies above on the slot's operands -- S == 1: attn_decode_kernel<true>'s, else
+// attn_decode_split_kernel<true>'s with the slot's own counters (cnt + b * heads) and parts -- so a slot's results are
+// theirs bit for bit.  A negative position is an EMPTY slot: its out row is zero (neg_fill), nothing else is written.
+__global__ __launch_bounds__(ATT_THREADS) void attn_decode_batch_kernel(const uint16_t* __restrict__ qkv,
+                                                                        uint16_t* __restrict__ k_cache,
+                                                                        uint16_t* __restrict__ v_cache,
+                                                                        const int64_t* __restrict__ pos,
+                                                                        const float* __restrict__ rope_rows,
+                                                                        uint16_t* __restrict__ out, int heads, int max_ctx, int S,
+                                                                        int* __restrict__ cnt, float* __restrict__ part) {
+    extern __shared__ float sm[];
+    __shared__ int last_s;
+    const int per = heads * S, b = blockIdx.x / per, r = blockIdx.x - b * per, h = r % heads, split = r / heads;
+    const int64_t hidden = (int64_t)heads * HD, cache = hidden * max_ctx;
+    qkv += b * 3 * hidden;
+    k_cache += b * cache;
+    v_cache += b * cache;
+    pos += b;
+    out += b * hidden;
+    const float* cos_r = rope_rows + (int64_t)b * HD;
+    if (S == 1)
+        attn_one_workgroup<true>(sm, h, qkv, k_cache, v_cache, pos, cos_r, cos_r + HD / 2, out, heads, max_ctx, 0, 0);
+    else
+        attn_split_workgroup<true>(sm, &last_s, h, split, qkv, k_cache, v_cache, pos, cos_r, cos_r + HD / 2, out, heads, max_ctx, S,
+                                   cnt + (int64_t)b * heads, part + (int64_t)b * heads * S * (HD + 2), 0);
+}
+
 // cos / sin of the CURRENT position -> one [2][HD/2] row (one launch per token; the position lives in device memory)
 // ... and, for the stage that owns the embedding, the token's embedding row in the same launch (tok nullable): a token's
 // two table look-ups are one small launch instead of two (each costs ~4.5 us of launch + cold round trip)
-__global__ __launch_bounds__(256) void rope_row_kernel(const int64_t* __restrict__ pos_p, const float* __restrict__ cos_t,
-                                                       const float* __restrict__ sin_t, float* __restrict__ row, int half_dim,
-                                                       int max_ctx, const int64_t* __restrict__ tok, const uint16_t* __restrict__ embed,
-                                                       int vocab, int hidden, uint16_t* __restrict__ h_out) {
+__device__ __forceinline__ void rope_row_gather(const int64_t* __restrict__ pos_p, const float* __restrict__ cos_t,
+                                                const float* __restrict__ sin_t, float* __restrict__ row, int half_dim,
+                                                int max_ctx, const int64_t* __restrict__ tok, const uint16_t* __restrict__ embed,
+                                                int vocab, int hidden, uint16_t* __restrict__ h_out) {
     int64_t pos = *pos_p;
     pos = pos < 0 ? 0 : pos >= max_ctx ? max_ctx - 1 : pos;    // (an out-of-range position is refused by the attention kernel itself)
     int64_t t = tok ? *tok : 0;
@@ -418,6 +463,83 @@ __global__ __launch_bounds__(256) void rope_row_kernel(const int64_t* __restrict
     }
     if (tok)
         for (int i = threadIdx.x; i < hidden / 8; i += 256) ((uint4*)h_out)[i] = ((const uint4*)(embed + t * hidden))[i];
+}
+__global__ __launch_bounds__(256) void rope_row_kernel(const int64_t* __restrict__ pos_p, const float* __restrict__ cos_t,
+                                                       const float* __restrict__ sin_t, float* __restrict__ row, int half_dim,
+                                                       int max_ctx, const int64_t* __restrict__ tok, const uint16_t* __restrict__ embed,
+                                                       int vocab, int hidden, uint16_t* __restrict__ h_out) {
+    rope_row_gather(pos_p, cos_t, sin_t, row, half_dim, max_ctx, tok, embed, vocab, hidden, h_out);
+}
+// ... for `batch` slots in one launch, workgroup b on pos[b], tok[b] (nullable), rows[b], h_out[b]: an empty slot's
+// negative position is clamped to 0 like any other
+__global__ __launch_bounds__(256) void rope_rows_kernel(const int64_t* __restrict__ pos, const float* __restrict__ cos_t,
+                                                        const float* __restrict__ sin_t, float* __restrict__ rows, int half_dim,
+                                                        int max_ctx, const int64_t* __restrict__ tok, const uint16_t* __restrict__ embed,
+                                                        int vocab, int hidden, uint16_t* __restrict__ h_out) {
+    const int b = blockIdx.x;
+    rope_row_gather(pos + b, cos_t, sin_t, rows + (int64_t)b * 2 * half_dim, half_dim, max_ctx, tok ? tok + b : nullptr, embed, vocab,
+                    hidden, h_out + (int64_t)b * hidden);
+}
+
+// The row-wise glue between the Linears of a BATCHED decode step (one token per sequence: the M = 1 GEMVs fold it into
+// their prologues, the M > 1 Linears do not), one launch each instead of ~8 / ~5 torch ones.
+// RMSNorm: y[r, k] = fp16(fp16(x[r, k] * inv_r) * norm_w[k]), inv_r = rsqrtf(sum_k x^2 / K + eps) in fp32 -- the arithmetic of
+// lmhead_argmax_kernel's prologue.  One workgroup per row; a thread's first two 8-column chunks (all of a K = 4096 row) stay
+// in registers between the two passes, further ones are read again.
+constexpr int ROWS_THREADS = 256;
+__global__ __launch_bounds__(ROWS_THREADS) void rmsnorm_rows_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ norm_w,
+                                                                    uint16_t* __restrict__ y, int K, float eps) {
+    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+    __shared__ float red[ROWS_THREADS / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, chunks = K / 8;
+    const h8* xr = (const h8*)(x + (int64_t)blockIdx.x * K);
+    const h8* g = (const h8*)norm_w;
+    h8* yr = (h8*)(y + (int64_t)blockIdx.x * K);
+    const h8 zero = {};
+    const h8 k0 = tid < chunks ? xr[tid] : zero, k1 = tid + ROWS_THREADS < chunks ? xr[tid + ROWS_THREADS] : zero;
+    float ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) ss += (float)k0[j] * (float)k0[j];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) ss += (float)k1[j] * (float)k1[j];
+    for (int i = tid + 2 * ROWS_THREADS; i < chunks; i += ROWS_THREADS) {
+        const h8 v = xr[i];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) ss += (float)v[j] * (float)v[j];
+    }
+    ss = wave_allsum(ss);
+    if (lane == 0) red[wave] = ss;
+    __syncthreads();
+    const float inv = rsqrtf((red[0] + red[1] + red[2] + red[3]) / (float)K + eps);
+    auto put = [&](int i, const h8& v) {
+        const h8 w = g[i];
+        h8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = (_Float16)((float)v[j] * inv) * w[j];
+        yr[i] = o;
+    };
+    if (tid < chunks) put(tid, k0);
+    if (tid + ROWS_THREADS < chunks) put(tid + ROWS_THREADS, k1);
+    for (int i = tid + 2 * ROWS_THREADS; i < chunks; i += ROWS_THREADS) put(i, xr[i]);
+}
+// SwiGLU: act[r, i] = fp16(fp16(silu(gate)) * up), silu(g) = g / (1 + exp(-g)) in fp32 (expf, not __expf: at g = -8 the
+// fast one's relative error grows with |g| past what the fp32 step may cost); gate_up [rows, 2 * inter] = gate | up.
+// ceil(inter / 8 / 256) workgroups per row, a thread per 8 columns.
+__global__ __launch_bounds__(ROWS_THREADS) void swiglu_rows_kernel(const uint16_t* __restrict__ gate_up, uint16_t* __restrict__ act,
+                                                                   int inter) {
+    typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+    const int per_row = (inter / 8 + ROWS_THREADS - 1) / ROWS_THREADS, r = blockIdx.x / per_row;
+    const int i = (blockIdx.x - r * per_row) * ROWS_THREADS + threadIdx.x;
+    if (i >= inter / 8) return;
+    const uint16_t* row = gate_up + (int64_t)r * 2 * inter;
+    const h8 gt = ((const h8*)row)[i], up = ((const h8*)(row + inter))[i];
+    h8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float gf = (float)gt[j];
+        o[j] = (_Float16)(gf / (1.0f + expf(-gf))) * up[j];
+    }
+    ((h8*)(act + (int64_t)r * inter))[i] = o;
 }
 
 // Final RMSNorm + lm_head (a plain fp16 Linear in the reference: MXQ quantises the decoder Linears only) + greedy
@@ -610,6 +732,40 @@ int mxq_launch_attn_decode_split_f16(const void* qkv, void* k_cache, void* v_cac
     attn_decode_split_kernel<true><<<heads * splits, ATT_THREADS, smem, stream>>>(
         (const uint16_t*)qkv, (uint16_t*)k_cache, (uint16_t*)v_cache, (const int64_t*)pos, (const float*)rope_row,
         (const float*)rope_row + HD / 2, (uint16_t*)out, heads, max_ctx, splits, cnt, part);
+    return (int)hipGetLastError();
+}
+
+// the batched decode step (mxq_attn_decode_batch_f16): ws = counters [batch * heads] (from byte 0), parts [batch * heads][splits][HD + 2]
+int mxq_launch_attn_decode_batch_f16(const void* qkv, void* k_cache, void* v_cache, const void* pos, const void* rope_rows,
+                                     void* out, int batch, int heads, int head_dim, int max_ctx, int splits, void* ws,
+                                     hipStream_t stream) {
+    if (head_dim != HD || splits < 1 || splits > MAX_SPLITS || (splits > 1 && !ws)) return (int)hipErrorInvalidValue;
+    const size_t smem = attn_smem(max_ctx);
+    hipError_t e = attn_lds_ceiling<&attn_decode_batch_kernel>(smem);
+    if (e != hipSuccess) return (int)e;
+    int* cnt = (int*)ws;
+    float* part = ws ? (float*)((char*)ws + (size_t)((batch * heads + 255) / 256) * 1024) : nullptr;
+    attn_decode_batch_kernel<<<heads * splits * batch, ATT_THREADS, smem, stream>>>(
+        (const uint16_t*)qkv, (uint16_t*)k_cache, (uint16_t*)v_cache, (const int64_t*)pos, (const float*)rope_rows, (uint16_t*)out,
+        heads, max_ctx, splits, cnt, part);
+    return (int)hipGetLastError();
+}
+
+int mxq_launch_rope_rows_f32(const void* pos, const void* cos_t, const void* sin_t, void* rows, int half_dim, int max_ctx,
+                             const void* tok, const void* embed, int vocab, int hidden, void* h_out, int batch, hipStream_t stream) {
+    rope_rows_kernel<<<batch, 256, 0, stream>>>((const int64_t*)pos, (const float*)cos_t, (const float*)sin_t, (float*)rows, half_dim,
+                                                max_ctx, (const int64_t*)tok, (const uint16_t*)embed, vocab, hidden, (uint16_t*)h_out);
+    return (int)hipGetLastError();
+}
+
+int mxq_launch_rmsnorm_rows_f16(const void* x, const void* norm_w, void* y, int rows, int K, float eps, hipStream_t stream) {
+    rmsnorm_rows_kernel<<<rows, ROWS_THREADS, 0, stream>>>((const uint16_t*)x, (const uint16_t*)norm_w, (uint16_t*)y, K, eps);
+    return (int)hipGetLastError();
+}
+
+int mxq_launch_swiglu_rows_f16(const void* gate_up, void* act, int rows, int inter, hipStream_t stream) {
+    swiglu_rows_kernel<<<(inter / 8 + ROWS_THREADS - 1) / ROWS_THREADS * rows, ROWS_THREADS, 0, stream>>>(
+        (const uint16_t*)gate_up, (uint16_t*)act, inter);
     return (int)hipGetLastError();
 }
 

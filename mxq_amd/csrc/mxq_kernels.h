@@ -190,6 +190,14 @@ int mxq_launch_attn_decode_f16(const void* qkv, void* k_cache, void* v_cache, co
 size_t mxq_attn_split_workspace_bytes_impl(int heads, int splits);
 int mxq_launch_attn_decode_split_f16(const void* qkv, void* k_cache, void* v_cache, const void* pos, const void* rope_row,
                                      void* out, int heads, int head_dim, int max_ctx, int splits, void* ws, hipStream_t stream);
+// batched decode (one token per sequence, `batch` sequences): csrc/decode_ops.hip
+int mxq_launch_attn_decode_batch_f16(const void* qkv, void* k_cache, void* v_cache, const void* pos, const void* rope_rows,
+                                     void* out, int batch, int heads, int head_dim, int max_ctx, int splits, void* ws,
+                                     hipStream_t stream);
+int mxq_launch_rope_rows_f32(const void* pos, const void* cos_t, const void* sin_t, void* rows, int half_dim, int max_ctx,
+                             const void* tok, const void* embed, int vocab, int hidden, void* h_out, int batch, hipStream_t stream);
+int mxq_launch_rmsnorm_rows_f16(const void* x, const void* norm_w, void* y, int rows, int K, float eps, hipStream_t stream);
+int mxq_launch_swiglu_rows_f16(const void* gate_up, void* act, int rows, int inter, hipStream_t stream);
 int mxq_launch_rope_row_f32(const void* pos, const void* cos_t, const void* sin_t, void* row, int half_dim, int max_ctx,
                             const void* tok, const void* embed, int vocab, int hidden, void* h_out, hipStream_t stream);
 // csrc/attn_prefill.hip: rope + KV append for `tokens` rows at pos0 .. (launch A), causal MFMA attention over the cache (launch B)

@@ -85,7 +85,7 @@ class DecodeStage:
         if arena:            # one allocation for the stage's packed weights, in streaming order (+0.35 %, tools/ab_decode.py)
             self._to_arena()
         n = len(self.layers)
-        self.k_cache = torch.zeros(n, heads, max_ctx, self.hd, device=dev, dtype=torch.float16)
+        self.k_cache = torch.zeros(self._cache_shape(n), device=dev, dtype=torch.float16)
         self.v_cache = torch.zeros_like(self.k_cache)
         self.norm_w = torch.ones(hidden, device=dev, dtype=torch.float16)
         inv = 1.0 / (10000 ** (torch.arange(0, self.hd, 2, device=dev).float() / self.hd))
@@ -118,6 +118,9 @@ class DecodeStage:
         self._head_tok = None
         self._h_in = torch.zeros(1, hidden, device=dev, dtype=torch.float16)
         self._h_out = torch.zeros(1, hidden, device=dev, dtype=torch.float16)
+
+    def _cache_shape(self, n_layers: int):
+        return (n_layers, self.heads, self.max_ctx, self.hd)
 
     def _to_arena(self):
         """All packed weights of the stage in ONE allocation, in the order a token streams them."""
@@ -251,33 +254,43 @@ class DecodeStage:
         csrc/attn_prefill.hip), o_proj + skip, RMSNorm, gate|up, SiLU * up, down_proj + skip.  Eager only; head dim 128 only
         (there is no torch attention fallback).  Raises RuntimeError, before any launch and with nothing changed, when the
         prompt does not fit the cache; a failure in a later launch leaves both positions where they were."""
+        self._check_prompt(h)
+        T = h.shape[0]
+        if T == 0:
+            return h.new_empty((0, self.hidden))
+        p0 = self.window.take(T)
+        try:
+            h = self._prefill_layers(h, self.k_cache, self.v_cache, p0)
+        except BaseException:
+            self.window.pos = p0               # nothing advanced the device position: the host mirror goes back with it (the
+            raise                              # cache rows from p0 on may be partly written; they are beyond the position)
+        self.pos += T
+        return h
+
+    def _check_prompt(self, h):
         if self.hd != 128:
             raise ValueError(f"prefill needs head dim 128 (csrc/attn_prefill.hip), this stage has {self.hd}")
         if h.dim() != 2 or h.shape[1] != self.hidden or h.dtype != torch.float16:
             raise ValueError(f"prefill takes fp16 [T, {self.hidden}], got {h.dtype} {tuple(h.shape)}")
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("prefill is eager only: the position is a host argument of its attention launch")
+
+    def _prefill_layers(self, h, k_cache, v_cache, p0: int):
+        """The layer loop of a prompt pass: rows h [T, hidden] at positions p0 .. p0 + T - 1 into the caches ``k_cache[i]`` /
+        ``v_cache[i]`` ([heads, max_ctx, 128], contiguous) of layer i.  Moves no position."""
         T = h.shape[0]
-        if T == 0:
-            return h.new_empty((0, self.hidden))
-        p0 = self.window.take(T)
         lib = _lib.load()
         st = torch.cuda.current_stream(self.dev).cuda_stream
-        try:
-            for i, (qkv, o, gu, down) in enumerate(self.w):
-                y = packing.linear(self._rms(h), qkv).contiguous()
-                a = torch.empty((T, self.hidden), dtype=torch.float16, device=self.dev)
-                _lib.check(lib.mxq_attn_prefill_f16(y.data_ptr(), self.k_cache[i].data_ptr(), self.v_cache[i].data_ptr(),
-                                                    self.cos.data_ptr(), self.sin.data_ptr(), a.data_ptr(), T, p0, self.heads,
-                                                    self.hd, self.max_ctx, st), "mxq_attn_prefill_f16")
-                h = h + packing.linear(a, o)
-                gu_y = packing.linear(self._rms(h), gu)
-                act = torch.nn.functional.silu(gu_y[:, : self.inter].float()).half() * gu_y[:, self.inter:]
-                h = h + packing.linear(act, down)
-        except BaseException:
-            self.window.pos = p0               # nothing advanced the device position: the host mirror goes back with it (the
-            raise                              # cache rows from p0 on may be partly written; they are beyond the position)
-        self.pos += T
+        for i, (qkv, o, gu, down) in enumerate(self.w):
+            y = packing.linear(self._rms(h), qkv).contiguous()
+            a = torch.empty((T, self.hidden), dtype=torch.float16, device=self.dev)
+            _lib.check(lib.mxq_attn_prefill_f16(y.data_ptr(), k_cache[i].data_ptr(), v_cache[i].data_ptr(),
+                                                self.cos.data_ptr(), self.sin.data_ptr(), a.data_ptr(), T, p0, self.heads,
+                                                self.hd, self.max_ctx, st), "mxq_attn_prefill_f16")
+            h = h + packing.linear(a, o)
+            gu_y = packing.linear(self._rms(h), gu)
+            act = torch.nn.functional.silu(gu_y[:, : self.inter].float()).half() * gu_y[:, self.inter:]
+            h = h + packing.linear(act, down)
         return h
 
     def prefill_tokens(self, ids):
@@ -414,6 +427,280 @@ class DecodeStage:
         self.pos.fill_(position)
         self.window.reset()
         self.window.take(position)
+
+
+class SlotTable:
+    """Host-side mirror of a batched stage's device positions: one ``ContextWindow`` per slot and an occupied flag.  Plain
+    Python (no tensors): every host entry point that fills, advances or frees a slot goes through it FIRST, so whatever
+    does not fit raises here, before any launch and with nothing changed."""
+
+    def __init__(self, batch: int, max_ctx: int, split_keys: int = 128):
+        if not 1 <= batch <= 256:
+            raise ValueError("batch must be 1..256 (include/mxq_hip.h: mxq_attn_decode_batch_f16)")
+        self.batch, self.max_ctx, self.split_keys = int(batch), int(max_ctx), int(split_keys)
+        self.windows = [ContextWindow(max_ctx) for _ in range(batch)]
+        self.occupied = [False] * batch
+
+    def _slot(self, b: int) -> int:
+        if not 0 <= b < self.batch:
+            raise IndexError(f"slot {b} outside 0..{self.batch - 1}")
+        return b
+
+    def position(self, b: int) -> int:
+        """The slot's position as the device holds it: -1 for an empty slot."""
+        return self.windows[b].pos if self.occupied[self._slot(b)] else -1
+
+    def positions(self) -> List[int]:
+        return [self.position(b) for b in range(self.batch)]
+
+    def fill(self, b: int, n: int) -> None:
+        """Occupy the empty slot ``b`` with a prompt of ``n`` positions."""
+        if self.occupied[self._slot(b)]:
+            raise RuntimeError(f"slot {b} is occupied (position {self.windows[b].pos}): release it first")
+        self.windows[b].reset()
+        self.windows[b].take(n)            # raises when the prompt does not fit; the slot stays empty
+        self.occupied[b] = True
+
+    def release(self, b: int) -> None:
+        self.occupied[self._slot(b)] = False
+        self.windows[b].reset()
+
+    def reset(self) -> None:
+        for b in range(self.batch):
+            self.release(b)
+
+    def check_step(self) -> None:
+        """A step appends one row to every occupied slot's cache: raise if one of them is full."""
+        for b in range(self.batch):
+            if self.occupied[b] and self.windows[b].pos >= self.max_ctx:
+                raise RuntimeError(f"slot {b}: decode position {self.windows[b].pos} is outside the KV cache (max_ctx = "
+                                   f"{self.max_ctx}); release the slot")
+
+    def take(self, n: int = 1) -> None:
+        """Every occupied slot moves on by ``n`` -- all of them or, if one does not fit, none."""
+        if n < 0:
+            raise ValueError("cannot take a negative number of positions")
+        for b in range(self.batch):
+            if self.occupied[b] and self.windows[b].pos + n > self.max_ctx:
+                raise RuntimeError(f"slot {b}: decode position {self.windows[b].pos} + {n} exceeds the KV cache (max_ctx = "
+                                   f"{self.max_ctx}); release the slot or build the stage with a larger max_ctx")
+        for b in range(self.batch):
+            if self.occupied[b]:
+                self.windows[b].take(n)
+
+    def longest(self) -> int:
+        """The largest occupied position, -1 when every slot is empty."""
+        return max(self.positions())
+
+    def splits(self, attn_splits: int, ahead: int = 0) -> int:
+        """``splits`` of the attention launch ``ahead`` steps from now: 1 while every occupied slot attends to at most
+        ``split_keys`` keys (position + 1), the stage's ``attn_splits`` otherwise."""
+        p = self.longest()
+        return attn_splits if (p >= 0 and p + ahead + 1 > self.split_keys) else 1
+
+
+class BatchedDecodeStage(DecodeStage):
+    """``DecodeStage`` for ``batch`` sequences per step, each in a slot with its own KV cache and position: the launches and
+    the packed-weight stream of a step are paid once for all of them.  Caches [layers, batch, heads, max_ctx, 128]; ``pos``
+    int64 [batch] on the device, -1 for an empty slot; ``slots`` (SlotTable) its host mirror.  Slots are filled by
+    ``prefill_slot`` / ``prefill_tokens_slot``, freed by ``release`` and may be refilled between steps or ``decode_tokens``
+    calls (continuous batching; when a sequence ends is the caller's decision).  Per layer a step launches
+    mxq_rmsnorm_rows_f16, q|k|v (``packing.linear``: the GEMV up to 4 rows, the skinny MFMA kernel beyond),
+    mxq_attn_decode_batch_f16, o + the residual add, mxq_rmsnorm_rows_f16, gate|up, mxq_swiglu_rows_f16, down + the residual
+    add.  Head dim 128, fp16, the mixed layout with exact metadata only."""
+
+    def __init__(self, layers, dev, batch: int, max_ctx: int = 512, hidden: int = LS.HIDDEN, inter: int = LS.INTERMEDIATE,
+                 heads: int = 32, first: bool = True, last: bool = True, vocab: int = 32000, arena: bool = True,
+                 weights_of: Optional[DecodeStage] = None):
+        if hidden != heads * 128:
+            raise ValueError(f"BatchedDecodeStage needs head dim 128, got {hidden} / {heads}")
+        if hidden % 8 or inter % 8:
+            raise ValueError("hidden and inter must be multiples of 8")
+        self.slots = SlotTable(batch, max_ctx, self.SPLIT_KEYS)        # (validates batch; _cache_shape needs it)
+        self.batch = int(batch)
+        # weights_of: share the packed weights of a stage over the same layers and sizes (built once, e.g. to compare the two)
+        if weights_of is not None and (list(weights_of.layers) != list(layers) or weights_of.compact or
+                                       (weights_of.hidden, weights_of.inter) != (hidden, inter)):
+            raise ValueError("weights_of must be a stage over the same layers and sizes, with exact metadata")
+        super().__init__(layers if weights_of is None else (), dev, max_ctx=max_ctx, hidden=hidden, inter=inter, heads=heads,
+                         first=first, last=last, vocab=vocab, fused=True, arena=arena)
+        if weights_of is not None:
+            self.layers, self.w = list(weights_of.layers), weights_of.w
+            self.k_cache = torch.zeros(self._cache_shape(len(self.layers)), device=dev, dtype=torch.float16)
+            self.v_cache = torch.zeros_like(self.k_cache)
+        self.window = None                                             # the single-sequence mirror: not this stage's
+        self.pos = torch.full((batch,), -1, dtype=torch.int64, device=dev)
+        self.rope_rows = torch.zeros(batch, 2 * (self.hd // 2), dtype=torch.float32, device=dev)
+        self.launches_per_layer = 10                                   # the eight above and the two residual adds
+        self._attn_ws = (torch.zeros(_lib.load().mxq_attn_batch_workspace_bytes(batch, heads, self.attn_splits), dtype=torch.uint8,
+                                     device=dev) if self.attn_splits > 1 else None)
+        self._h_in = torch.zeros(batch, hidden, device=dev, dtype=torch.float16)
+        self._h_out = None
+        self._tgraph = self._tgraph_long = None
+
+    def _cache_shape(self, n_layers: int):
+        return (n_layers, self.batch, self.heads, self.max_ctx, self.hd)
+
+    def _st(self):
+        return torch.cuda.current_stream(self.dev).cuda_stream
+
+    def _single_only(self, *args, **kwargs):
+        raise RuntimeError("a single-sequence entry of DecodeStage: BatchedDecodeStage has prefill_slot / prefill_tokens_slot, "
+                           "step + advance, capture_token_loop + decode_tokens, seek_slot")
+    prefill = prefill_tokens = capture = step_graph = seek = _single_only
+
+    def _rms_rows(self, x):
+        y = torch.empty_like(x)
+        _lib.check(_lib.load().mxq_rmsnorm_rows_f16(x.data_ptr(), self.norm_w.data_ptr(), y.data_ptr(), x.shape[0], self.hidden, 1e-5,
+                                                    self._st()), "mxq_rmsnorm_rows_f16")
+        return y
+
+    def _gather_rows(self, tokens=None):
+        """cos | sin of every slot's own position -> rope_rows, once per step; with ``tokens`` (int64 [batch]) also their
+        embedding rows -> _h_in, in the same launch."""
+        e = self.embed if tokens is not None else None
+        _lib.check(_lib.load().mxq_embed_rope_rows(tokens.data_ptr() if tokens is not None else None,
+                                                   e.data_ptr() if e is not None else None, e.shape[0] if e is not None else 0,
+                                                   self.hidden, self._h_in.data_ptr() if e is not None else None, self.pos.data_ptr(),
+                                                   self.cos.data_ptr(), self.sin.data_ptr(), self.rope_rows.data_ptr(), self.hd // 2,
+                                                   self.max_ctx, self.batch, self._st()), "mxq_embed_rope_rows")
+
+    def embed_token(self, tok):
+        return self.embed.index_select(0, tok.clamp(0, self.embed.shape[0] - 1))      # (an empty slot's id is -1)
+
+    def head(self, h, out: Optional[torch.Tensor] = None):
+        """Final RMSNorm (mxq_rmsnorm_rows_f16) + lm_head (``F.linear``) + greedy argmax -> ids int64 [rows]."""
+        ids = torch.nn.functional.linear(self._rms_rows(h.contiguous()), self.lm_head).argmax(dim=-1)
+        return ids if out is None else out.copy_(ids)
+
+    def step(self, h, rope_done: bool = False):
+        """One token of every slot through this stage's layers.  h [batch, hidden] fp16 -> [batch, hidden]; the rows of empty
+        slots are unspecified and influence no other row.  Raises RuntimeError before any launch when an occupied slot is full."""
+        if h.shape != (self.batch, self.hidden) or h.dtype != torch.float16:
+            raise ValueError(f"step takes fp16 [{self.batch}, {self.hidden}], got {h.dtype} {tuple(h.shape)}")
+        self.slots.check_step()
+        if self._pin_long is not None:
+            self._long_ctx = self._pin_long                                    # capture and its eager pre-run: pinned
+        elif not torch.cuda.is_current_stream_capturing():
+            self._long_ctx = self.slots.splits(self.attn_splits) > 1           # eager step: the host knows the positions
+        splits = self.attn_splits if self._long_ctx else 1
+        if not rope_done:
+            self._gather_rows()
+        lib, B = _lib.load(), self.batch
+        ws = self._attn_ws.data_ptr() if self._attn_ws is not None else None
+        h = h.contiguous()
+        for i, (qkv, o, gu, down) in enumerate(self.w):
+            y = packing.linear(self._rms_rows(h), qkv)
+            a = torch.empty((B, self.hidden), dtype=torch.float16, device=self.dev)
+            _lib.check(lib.mxq_attn_decode_batch_f16(y.data_ptr(), self.k_cache[i].data_ptr(), self.v_cache[i].data_ptr(),
+                                                     self.pos.data_ptr(), self.rope_rows.data_ptr(), a.data_ptr(), B, self.heads,
+                                                     self.hd, self.max_ctx, splits, ws, self._st()), "mxq_attn_decode_batch_f16")
+            h = h + packing.linear(a, o)
+            g = packing.linear(self._rms_rows(h), gu)
+            act = torch.empty((B, self.inter), dtype=torch.float16, device=self.dev)
+            _lib.check(lib.mxq_swiglu_rows_f16(g.data_ptr(), act.data_ptr(), B, self.inter, self._st()), "mxq_swiglu_rows_f16")
+            h = h + packing.linear(act, down)
+        return h
+
+    def _advance_device(self):
+        self.pos += (self.pos >= 0)
+
+    def advance(self):
+        """Every occupied slot moves on by one; an occupied slot that is full raises before anything changes."""
+        self.slots.take(1)
+        self._advance_device()
+
+    def prefill_slot(self, b: int, h):
+        """A prompt of T tokens into the EMPTY slot ``b``: h [T, hidden] fp16 -> [T, hidden] through ``DecodeStage.prefill``'s
+        layer loop on the slot's caches; the slot is occupied at position T afterwards.  Raises RuntimeError, before any launch
+        and with nothing changed, when the prompt does not fit or the slot is occupied."""
+        self._check_prompt(h)
+        T = h.shape[0]
+        self.slots.fill(b, T)
+        try:
+            if T:
+                h = self._prefill_layers(h, self.k_cache[:, b], self.v_cache[:, b], 0)
+        except BaseException:
+            self.slots.release(b)              # (the device position was never set: the slot is still empty there)
+            raise
+        self.pos[b] = T
+        return h
+
+    def prefill_tokens_slot(self, b: int, ids):
+        """Prompt ids (int64 [T], T >= 1) into the empty slot ``b`` -> the slot's first generated id (tensor [1])."""
+        if getattr(self, "embed", None) is None or getattr(self, "lm_head", None) is None:
+            raise ValueError("prefill_tokens_slot needs the first and the last stage in one process")
+        ids = torch.as_tensor(ids, dtype=torch.int64, device=self.dev).reshape(-1)
+        if ids.numel() == 0:
+            raise ValueError("prefill_tokens_slot needs at least one prompt token")
+        h = self.prefill_slot(b, self.embed_token(ids))
+        return self.head(h[-1:]).reshape(-1)[:1]
+
+    def release(self, b: int):
+        """Free slot ``b``: its position becomes -1; its cache rows are left as they are (the next prompt overwrites them)."""
+        self.slots.release(b)
+        self.pos[b] = -1
+
+    def reset(self):
+        self.slots.reset()
+        self.pos.fill_(-1)
+        self.k_cache.zero_()
+        self.v_cache.zero_()
+
+    def seek_slot(self, b: int, position: int, seed: int = 5):
+        """Benchmark helper: occupy the empty slot ``b`` as if ``position`` tokens had been decoded (seeded random cache rows)."""
+        if not 0 <= position < self.max_ctx:
+            raise ValueError("position outside the KV cache")
+        self.slots.fill(b, position)
+        g = torch.Generator(device=self.dev).manual_seed(seed + b)
+        for c in (self.k_cache, self.v_cache):
+            c[:, b, :, :position].copy_(torch.randn(c[:, b, :, :position].shape, generator=g, device=self.dev).half())
+        self.pos[b] = position
+
+    def capture_token_loop(self, token_buf: torch.Tensor):
+        """Capture ids -> embedding + rotary rows -> layers -> final norm + lm_head + argmax -> ids -> advance as the short /
+        long pair of hipGraphs, updating ``token_buf`` (int64 [batch], -1 in the columns of empty slots) in place.  Call it
+        while every slot is empty: the warm-up runs write the first cache rows of every slot and overwrite ``token_buf``."""
+        if getattr(self, "embed", None) is None or getattr(self, "lm_head", None) is None:
+            raise ValueError("capture_token_loop needs the first and the last stage in one process")
+        if token_buf.dtype != torch.int64 or token_buf.shape != (self.batch,) or not token_buf.is_contiguous():
+            raise ValueError(f"token_buf must be a contiguous int64 [{self.batch}] tensor")
+        if any(self.slots.occupied):
+            raise RuntimeError("capture_token_loop needs every slot empty")
+
+        def one():
+            self._gather_rows(token_buf)
+            ids = self.head(self.step(self._h_in, rope_done=True))
+            token_buf.copy_(torch.where(self.pos >= 0, ids, -1))
+            self._advance_device()
+        self.pos.zero_()                       # warm-up on real positions (the host mirror stays empty: nothing is reserved)
+        for _ in range(2):
+            one()
+        self.pos.zero_()
+        torch.cuda.synchronize()
+        try:
+            self._tgraph, self._tgraph_long = self._capture_short_and_long(one)
+        finally:
+            self.pos.fill_(-1)
+        return self
+
+    def decode_tokens(self, token_buf: torch.Tensor, first_tokens, n_tokens: int):
+        """Greedy decode of ``n_tokens`` tokens per occupied slot with the graphs of ``capture_token_loop``, from
+        ``first_tokens`` (int64 [batch]; the entries of empty slots are ignored) -> ids int64 [n_tokens, batch] on the
+        device, -1 in the columns of empty slots.  Raises before any launch when an occupied slot cannot hold them."""
+        if self._tgraph is None:
+            raise RuntimeError("capture_token_loop first")
+        first = torch.as_tensor(first_tokens, dtype=torch.int64, device=self.dev).reshape(-1)
+        if first.numel() != self.batch:
+            raise ValueError(f"first_tokens must hold {self.batch} ids")
+        long_ = [self._tgraph_long is not None and self.slots.splits(self.attn_splits, ahead=i) > 1 for i in range(n_tokens)]
+        self.slots.take(n_tokens)              # every replay advances the occupied device positions by one
+        token_buf.copy_(first)
+        out = torch.empty((n_tokens, self.batch), dtype=torch.int64, device=self.dev)
+        for i in range(n_tokens):
+            (self._tgraph_long if long_[i] else self._tgraph).replay()
+            out[i].copy_(token_buf)
+        return out
 
 
 def decode_pipeline_figure(pipe, dev, tokens: int = 32, ctx: int = 64, layers: int = LS.N_LAYERS, compact: bool = False,
