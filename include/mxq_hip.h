@@ -554,6 +554,60 @@ int mxq_kv_append_rope_f16(const void* qkv, void* k_cache, void* v_cache, const 
 int mxq_attn_prefill_f16(const void* qkv, void* k_cache, void* v_cache, const void* cos_t, const void* sin_t, void* out,
                          int tokens, int pos0, int heads, int head_dim, int max_ctx, void* stream);
 
+/* Int8 KV cache (csrc/attn_kv8.hip): the STORED form of the caches above for the batched decode path.
+ * THE FORMAT.  Per slot and layer, for K and V each: codes int8 [heads][max_ctx][128], two's complement; scale f32
+ * [heads][max_ctx]; batched, both carry a leading [batch] dimension as the fp16 caches do.  A row costs 132 bytes against 256.
+ * One row is one (position, head) vector of 128 fp16 values x -- the very row the fp16 entries append: the value row of qkv as
+ * it is, the key row rotated with the decode entries' arithmetic and rounded once to fp16 -- quantised in IEEE fp32 with true
+ * divisions, no contraction and no reciprocal approximation:
+ *     amax   = max_d |x_d|                                  (exact; fp16 -> fp32)
+ *     scale  = amax / 127.0f,   inv = 127.0f / amax
+ *     code_d = (int8) clamp(rintf(x_d * inv), -127, 127)     (ties to even)
+ *     amax == 0       : scale = 0, every code 0 (no division)
+ *     amax not finite : scale = NaN, every code 0 -- the row reads back as NaN (qkv is documented as finite, as for prefill)
+ *     value read back : (float)code_d * scale               (fp32)
+ * This is the symmetric quantiser with one range per group of 128 = one head that the reference names "groupwise", placed
+ * where a cache can store it.  It is the cache's storage format, NOT a restatement of the reference's SymQuantizer fake-quant
+ * (LLM-QAT/models/modeling_llama_quant.py:322-329, reproduced bit-exactly by mxq_actquant_*), from which it differs on purpose:
+ * the reference quantises K BEFORE the rotary embedding (a cache of pre-rotation codes would have to rotate every key on every
+ * read), takes one range per token over all heads, and divides by s + 1e-6.  Only 8 bit; head dim 128; fp16 activations.
+ *
+ * mxq_attn_decode_batch_kv8_f16: mxq_attn_decode_batch_f16 over that cache.  qkv, pos, rope_rows, out, batch, splits, the grid,
+ * the slot layout, the partition of a slot's keys (64-key units, trailing splits empty), the last-arriver merge and the
+ * workspace (mxq_attn_batch_workspace_bytes(batch, heads, splits), counter head zeroed once, left zeroed; nullable when
+ * splits == 1) are that entry's.  ONE algorithm at every length -- the partition applies from the first key on, there is no
+ * 128-key switch to fp16 probabilities; a (slot, head) whose keys fall into one split is written by that split directly and
+ * does not touch the workspace.  The split that owns position pos[b] appends: it rotates k, quantises the k and v rows,
+ * writes their codes (16-byte stores) and the two scales at row pos[b], and uses its own row in the dequantised form, from
+ * on-chip memory -- so a step sees exactly what every later step and a prefill will read.  No other workgroup reads or writes
+ * row pos[b] in the launch.  Rounding points: q16 as the fp16 entries compute it; score_j = (sum_d q16_d * code_jd, fp32
+ * accumulation) * scale_j * rsqrtf(128), kept in fp32 (not rounded to fp16, as in the prefill kernel); probabilities fp32 with
+ * __expf; o = sum_j p_j * vscale_j * code_jd in fp32; parts merged in fp32, in split order; ONE fp16 rounding of out.  A
+ * repeated launch is bit-identical.  pos[b] < 0 (an empty slot): nothing written, a zero out row; pos[b] >= max_ctx (refused):
+ * nothing written, a NaN out row; both decided before any barrier.  Validation and alignment as mxq_attn_decode_batch_f16; in
+ * addition codes 16 bytes, scales 4.  Stream-ordered, no allocation, hipGraph-replayable.
+ * mxq_kv8_append_rope_f16: the quantising form of mxq_kv_append_rope_f16 (one launch): codes and scales of rows pos0 ..
+ * pos0 + tokens - 1 BIT-IDENTICAL to what the decode entry above appends for the same qkv row and position.
+ * mxq_kv8_expand_f16: rows [0, rows) of every head of one quantised cache -> an fp16 cache out16 [heads][max_ctx][128], each
+ * element fp16((float)code * scale), the fp32 product rounded once; rows at and beyond `rows` are not written.
+ * mxq_attn_prefill_kv8_f16 (four launches, stream order the only synchronisation): the quantising append; the expansion of rows
+ * [0, pos0 + tokens) of K and of V into the caller's two fp16 scratch caches ([heads][max_ctx][128] each); then
+ * mxq_attn_prefill_f16's causal attention launch, unchanged, over the scratch -- so prompt tokens attend over quantised keys and
+ * values as decode steps do.  The project's hoisted-dequant pattern, not tuned.  The keys and values that launch reads carry one
+ * more fp16 rounding (<= 2^-11 relative) than the decode kernel's fp32 code * scale.
+ * Validation, before anything is launched: MXQ_E_NULL; MXQ_E_SHAPE as the fp16 entries (mxq_kv8_expand_f16: rows < 1 or
+ * > max_ctx, heads <= 0, max_ctx <= 0 or > 32768); MXQ_E_ALIGN: codes, scratch, out16 16 bytes, scales 4, the rest as the fp16
+ * entries. */
+int mxq_attn_decode_batch_kv8_f16(const void* qkv, void* k_codes, void* k_scale, void* v_codes, void* v_scale, const void* pos,
+                                  const void* rope_rows, void* out, int batch, int heads, int head_dim, int max_ctx, int splits,
+                                  void* workspace, void* stream);
+int mxq_kv8_append_rope_f16(const void* qkv, void* k_codes, void* k_scale, void* v_codes, void* v_scale, const void* cos_t,
+                            const void* sin_t, int tokens, int pos0, int heads, int head_dim, int max_ctx, void* stream);
+int mxq_kv8_expand_f16(const void* codes, const void* scale, void* out16, int rows, int heads, int max_ctx, void* stream);
+int mxq_attn_prefill_kv8_f16(const void* qkv, void* k_codes, void* k_scale, void* v_codes, void* v_scale, const void* cos_t,
+                             const void* sin_t, void* out, void* k_scratch, void* v_scratch, int tokens, int pos0, int heads,
+                             int head_dim, int max_ctx, void* stream);
+
 /* Decode-harness glue (BASELINE config 3), not part of the reference's hot path: final RMSNorm + the fp16 lm_head
  * Linear + greedy argmax of ONE token.  h fp16[K], norm_w fp16[K], w fp16[V, K] (row-major nn.Linear weight), K = 4096;
  * the normalised row is fp16(h * rsqrt(mean h^2 + eps)) * norm_w, a logit the fp32 dot rounded to fp16, the result

@@ -298,6 +298,64 @@ int mxq_attn_prefill_f16(const void* qkv, void* k_cache, void* v_cache, const vo
     return mxq_launch_attn_prefill_f16(qkv, k_cache, v_cache, cos_t, sin_t, out, tokens, pos0, heads, max_ctx, (hipStream_t)stream);
 }
 
+// int8 KV cache (csrc/attn_kv8.hip): codes 16-byte aligned, scales 4; everything else as the fp16 entries above
+static bool kv8_null(const void* kc, const void* ks, const void* vc, const void* vs) { return !kc || !ks || !vc || !vs; }
+static bool kv8_aligned(const void* kc, const void* ks, const void* vc, const void* vs) {
+    return aligned16(kc) && aligned16(vc) && aligned4(ks) && aligned4(vs);
+}
+
+int mxq_attn_decode_batch_kv8_f16(const void* qkv, void* k_codes, void* k_scale, void* v_codes, void* v_scale, const void* pos,
+                                  const void* rope_rows, void* out, int batch, int heads, int head_dim, int max_ctx, int splits,
+                                  void* workspace, void* stream) {
+    if (!qkv || kv8_null(k_codes, k_scale, v_codes, v_scale) || !pos || !rope_rows || !out) return MXQ_E_NULL;
+    if (batch < 1 || batch > 256 || heads <= 0 || (int64_t)batch * heads > (1 << 20) || head_dim != 128 || max_ctx <= 0 ||
+        max_ctx > 32768 || splits < 1 || splits > 16 || (splits > 1 && !workspace))
+        return MXQ_E_SHAPE;
+    if (!kv8_aligned(k_codes, k_scale, v_codes, v_scale) || (workspace && !aligned16(workspace)) || ((uintptr_t)pos & 7) ||
+        !aligned4(rope_rows) || ((uintptr_t)qkv & 1) || ((uintptr_t)out & 1))
+        return MXQ_E_ALIGN;
+    return mxq_launch_attn_decode_batch_kv8_f16(qkv, k_codes, k_scale, v_codes, v_scale, pos, rope_rows, out, batch, heads, max_ctx,
+                                                splits, workspace, (hipStream_t)stream);
+}
+
+// the prompt entries' shared validation: qkv (and out, scratch) 16 bytes as mxq_attn_prefill_f16, the tables 4
+static int kv8_prefill_check(const void* qkv, const void* k_codes, const void* k_scale, const void* v_codes, const void* v_scale,
+                             const void* cos_t, const void* sin_t, int tokens, int pos0, int heads, int head_dim, int max_ctx) {
+    if (!qkv || kv8_null(k_codes, k_scale, v_codes, v_scale) || !cos_t || !sin_t) return MXQ_E_NULL;
+    if (tokens <= 0 || heads <= 0 || head_dim != 128 || max_ctx <= 0 || max_ctx > 32768 || pos0 < 0 || pos0 > max_ctx - tokens)
+        return MXQ_E_SHAPE;
+    if (!aligned16(qkv) || !kv8_aligned(k_codes, k_scale, v_codes, v_scale) || !aligned4(cos_t) || !aligned4(sin_t)) return MXQ_E_ALIGN;
+    return 0;
+}
+
+int mxq_kv8_append_rope_f16(const void* qkv, void* k_codes, void* k_scale, void* v_codes, void* v_scale, const void* cos_t,
+                            const void* sin_t, int tokens, int pos0, int heads, int head_dim, int max_ctx, void* stream) {
+    if (int e = kv8_prefill_check(qkv, k_codes, k_scale, v_codes, v_scale, cos_t, sin_t, tokens, pos0, heads, head_dim, max_ctx)) return e;
+    return mxq_launch_kv8_append_rope_f16(qkv, k_codes, k_scale, v_codes, v_scale, cos_t, sin_t, tokens, pos0, heads, max_ctx,
+                                          (hipStream_t)stream);
+}
+
+int mxq_kv8_expand_f16(const void* codes, const void* scale, void* out16, int rows, int heads, int max_ctx, void* stream) {
+    if (!codes || !scale || !out16) return MXQ_E_NULL;
+    if (rows <= 0 || heads <= 0 || max_ctx <= 0 || max_ctx > 32768 || rows > max_ctx) return MXQ_E_SHAPE;
+    if (!aligned16(codes) || !aligned4(scale) || !aligned16(out16)) return MXQ_E_ALIGN;
+    return mxq_launch_kv8_expand_f16(codes, scale, out16, rows, heads, max_ctx, (hipStream_t)stream);
+}
+
+int mxq_attn_prefill_kv8_f16(const void* qkv, void* k_codes, void* k_scale, void* v_codes, void* v_scale, const void* cos_t,
+                             const void* sin_t, void* out, void* k_scratch, void* v_scratch, int tokens, int pos0, int heads,
+                             int head_dim, int max_ctx, void* stream) {
+    if (!out || !k_scratch || !v_scratch) return MXQ_E_NULL;
+    if (int e = kv8_prefill_check(qkv, k_codes, k_scale, v_codes, v_scale, cos_t, sin_t, tokens, pos0, heads, head_dim, max_ctx)) return e;
+    if (!aligned16(out) || !aligned16(k_scratch) || !aligned16(v_scratch)) return MXQ_E_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    if (int e = mxq_launch_kv8_append_rope_f16(qkv, k_codes, k_scale, v_codes, v_scale, cos_t, sin_t, tokens, pos0, heads, max_ctx, st))
+        return e;
+    if (int e = mxq_launch_kv8_expand_f16(k_codes, k_scale, k_scratch, pos0 + tokens, heads, max_ctx, st)) return e;
+    if (int e = mxq_launch_kv8_expand_f16(v_codes, v_scale, v_scratch, pos0 + tokens, heads, max_ctx, st)) return e;
+    return mxq_launch_attn_prefill_f16(qkv, k_scratch, v_scratch, cos_t, sin_t, out, tokens, pos0, heads, max_ctx, st);
+}
+
 int mxq_lmhead_argmax_f16(const void* h, const void* norm_w, float eps, const void* w, int V, int K, void* part,
                           int part_slots, void* token, void* stream) {
     if (!h || !norm_w || !w || !part || !token) return MXQ_E_NULL;

@@ -205,6 +205,15 @@ int mxq_launch_kv_append_rope_f16(const void* qkv, void* k_cache, void* v_cache,
                                   int pos0, int heads, int max_ctx, hipStream_t stream);
 int mxq_launch_attn_prefill_f16(const void* qkv, const void* k_cache, const void* v_cache, const void* cos_t, const void* sin_t,
                                 void* out, int tokens, int pos0, int heads, int max_ctx, hipStream_t stream);
+// csrc/attn_kv8.hip: the int8 KV cache (include/mxq_hip.h) -- batched decode over codes and scales, the quantising append of a
+// prompt's rows, the expansion of rows [0, rows) of every head into an fp16 cache
+int mxq_launch_attn_decode_batch_kv8_f16(const void* qkv, void* k_codes, void* k_scale, void* v_codes, void* v_scale, const void* pos,
+                                         const void* rope_rows, void* out, int batch, int heads, int max_ctx, int splits, void* ws,
+                                         hipStream_t stream);
+int mxq_launch_kv8_append_rope_f16(const void* qkv, void* k_codes, void* k_scale, void* v_codes, void* v_scale, const void* cos_t,
+                                   const void* sin_t, int tokens, int pos0, int heads, int max_ctx, hipStream_t stream);
+int mxq_launch_kv8_expand_f16(const void* codes, const void* scale, void* out16, int rows, int heads, int max_ctx,
+                              hipStream_t stream);
 int mxq_launch_fakequant_fwd(const void* w, void* out, int rows, int cols, int num_bits, int dtype,
                              hipStream_t stream);
 int mxq_launch_fakequant_bwd(const void* grad_out, const void* w, void* grad_in, int64_t n, float lo, float hi,

@@ -84,9 +84,7 @@ class DecodeStage:
             self.w.append((qkv, o, gu, down))
         if arena:            # one allocation for the stage's packed weights, in streaming order (+0.35 %, tools/ab_decode.py)
             self._to_arena()
-        n = len(self.layers)
-        self.k_cache = torch.zeros(self._cache_shape(n), device=dev, dtype=torch.float16)
-        self.v_cache = torch.zeros_like(self.k_cache)
+        self._alloc_caches(len(self.layers))
         self.norm_w = torch.ones(hidden, device=dev, dtype=torch.float16)
         inv = 1.0 / (10000 ** (torch.arange(0, self.hd, 2, device=dev).float() / self.hd))
         ang = torch.arange(max_ctx, device=dev).float()[:, None] * inv[None, :]
@@ -121,6 +119,10 @@ class DecodeStage:
 
     def _cache_shape(self, n_layers: int):
         return (n_layers, self.heads, self.max_ctx, self.hd)
+
+    def _alloc_caches(self, n_layers: int):
+        self.k_cache = torch.zeros(self._cache_shape(n_layers), device=self.dev, dtype=torch.float16)
+        self.v_cache = torch.zeros_like(self.k_cache)
 
     def _to_arena(self):
         """All packed weights of the stage in ONE allocation, in the order a token streams them."""
@@ -284,14 +286,18 @@ class DecodeStage:
         for i, (qkv, o, gu, down) in enumerate(self.w):
             y = packing.linear(self._rms(h), qkv).contiguous()
             a = torch.empty((T, self.hidden), dtype=torch.float16, device=self.dev)
-            _lib.check(lib.mxq_attn_prefill_f16(y.data_ptr(), k_cache[i].data_ptr(), v_cache[i].data_ptr(),
-                                                self.cos.data_ptr(), self.sin.data_ptr(), a.data_ptr(), T, p0, self.heads,
-                                                self.hd, self.max_ctx, st), "mxq_attn_prefill_f16")
+            self._prefill_attn(lib, y, k_cache[i], v_cache[i], a, T, p0, st)
             h = h + packing.linear(a, o)
             gu_y = packing.linear(self._rms(h), gu)
             act = torch.nn.functional.silu(gu_y[:, : self.inter].float()).half() * gu_y[:, self.inter:]
             h = h + packing.linear(act, down)
         return h
+
+    def _prefill_attn(self, lib, y, k_cache, v_cache, a, T: int, p0: int, st):
+        """RoPE + cache append + causal attention of one layer's prompt rows y [T, 3 * hidden] -> a [T, hidden]."""
+        _lib.check(lib.mxq_attn_prefill_f16(y.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), self.cos.data_ptr(),
+                                            self.sin.data_ptr(), a.data_ptr(), T, p0, self.heads, self.hd, self.max_ctx, st),
+                   "mxq_attn_prefill_f16")
 
     def prefill_tokens(self, ids):
         """Prompt ids (int64 [T], T >= 1) -> the first generated token id (tensor [1]): embedding, ``prefill``, ``head`` on
@@ -507,11 +513,21 @@ class BatchedDecodeStage(DecodeStage):
     calls (continuous batching; when a sequence ends is the caller's decision).  Per layer a step launches
     mxq_rmsnorm_rows_f16, q|k|v (``packing.linear``: the GEMV up to 4 rows, the skinny MFMA kernel beyond),
     mxq_attn_decode_batch_f16, o + the residual add, mxq_rmsnorm_rows_f16, gate|up, mxq_swiglu_rows_f16, down + the residual
-    add.  Head dim 128, fp16, the mixed layout with exact metadata only."""
+    add.  Head dim 128, fp16, the mixed layout with exact metadata only.
+
+    ``kv_bits`` = 8: the caches are STORED quantised (include/mxq_hip.h, "Int8 KV cache": int8 codes and one f32 scale per
+    (position, head) row, 132 bytes against 256) -- ``k_codes`` / ``v_codes`` int8 [layers, batch, heads, max_ctx, 128],
+    ``k_scale`` / ``v_scale`` f32 [layers, batch, heads, max_ctx]; there is no ``k_cache`` / ``v_cache``.  A step's attention is
+    mxq_attn_decode_batch_kv8_f16, a prompt's mxq_attn_prefill_kv8_f16 over ONE pair of fp16 scratch caches [heads, max_ctx,
+    128] shared by all layers and slots (a prompt pass expands the slot's rows into it layer by layer).  16 (the default):
+    the fp16 caches above."""
 
     def __init__(self, layers, dev, batch: int, max_ctx: int = 512, hidden: int = LS.HIDDEN, inter: int = LS.INTERMEDIATE,
                  heads: int = 32, first: bool = True, last: bool = True, vocab: int = 32000, arena: bool = True,
-                 weights_of: Optional[DecodeStage] = None):
+                 weights_of: Optional[DecodeStage] = None, kv_bits: int = 16):
+        if kv_bits not in (16, 8):
+            raise ValueError(f"kv_bits must be 16 (fp16 caches) or 8 (int8 codes + f32 row scales), got {kv_bits!r}")
+        self.kv_bits = int(kv_bits)
         if hidden != heads * 128:
             raise ValueError(f"BatchedDecodeStage needs head dim 128, got {hidden} / {heads}")
         if hidden % 8 or inter % 8:
@@ -526,8 +542,7 @@ class BatchedDecodeStage(DecodeStage):
                          first=first, last=last, vocab=vocab, fused=True, arena=arena)
         if weights_of is not None:
             self.layers, self.w = list(weights_of.layers), weights_of.w
-            self.k_cache = torch.zeros(self._cache_shape(len(self.layers)), device=dev, dtype=torch.float16)
-            self.v_cache = torch.zeros_like(self.k_cache)
+            self._alloc_caches(len(self.layers))
         self.window = None                                             # the single-sequence mirror: not this stage's
         self.pos = torch.full((batch,), -1, dtype=torch.int64, device=dev)
         self.rope_rows = torch.zeros(batch, 2 * (self.hd // 2), dtype=torch.float32, device=dev)
@@ -540,6 +555,27 @@ class BatchedDecodeStage(DecodeStage):
 
     def _cache_shape(self, n_layers: int):
         return (n_layers, self.batch, self.heads, self.max_ctx, self.hd)
+
+    def _alloc_caches(self, n_layers: int):
+        if self.kv_bits == 16:
+            return super()._alloc_caches(n_layers)
+        shape = self._cache_shape(n_layers)
+        self.k_codes = torch.zeros(shape, device=self.dev, dtype=torch.int8)
+        self.v_codes = torch.zeros_like(self.k_codes)
+        self.k_scale = torch.zeros(shape[:-1], device=self.dev, dtype=torch.float32)
+        self.v_scale = torch.zeros_like(self.k_scale)
+        # the prefill attention's fp16 view of ONE slot and layer at a time: mxq_attn_prefill_kv8_f16 expands into it
+        self._k_scratch = torch.zeros(shape[2:], device=self.dev, dtype=torch.float16)
+        self._v_scratch = torch.zeros_like(self._k_scratch)
+
+    def _kv_tensors(self):
+        return (self.k_cache, self.v_cache) if self.kv_bits == 16 else (self.k_codes, self.k_scale, self.v_codes, self.v_scale)
+
+    def kv_cache_bytes(self) -> int:
+        """Bytes of the stored KV cache of all layers and slots: 2 * 256 per (layer, slot, head, position) in fp16, 2 * 132 as
+        int8 codes + an f32 scale.  The int8 stage's one pair of fp16 scratch caches (2 * heads * max_ctx * 256 bytes,
+        whatever the number of layers and slots) is working memory of a prompt pass, not part of the cache, and not counted."""
+        return sum(t.numel() * t.element_size() for t in self._kv_tensors())
 
     def _st(self):
         return torch.cuda.current_stream(self.dev).cuda_stream
@@ -592,9 +628,16 @@ class BatchedDecodeStage(DecodeStage):
         for i, (qkv, o, gu, down) in enumerate(self.w):
             y = packing.linear(self._rms_rows(h), qkv)
             a = torch.empty((B, self.hidden), dtype=torch.float16, device=self.dev)
-            _lib.check(lib.mxq_attn_decode_batch_f16(y.data_ptr(), self.k_cache[i].data_ptr(), self.v_cache[i].data_ptr(),
-                                                     self.pos.data_ptr(), self.rope_rows.data_ptr(), a.data_ptr(), B, self.heads,
-                                                     self.hd, self.max_ctx, splits, ws, self._st()), "mxq_attn_decode_batch_f16")
+            if self.kv_bits == 8:
+                _lib.check(lib.mxq_attn_decode_batch_kv8_f16(y.data_ptr(), self.k_codes[i].data_ptr(), self.k_scale[i].data_ptr(),
+                                                             self.v_codes[i].data_ptr(), self.v_scale[i].data_ptr(),
+                                                             self.pos.data_ptr(), self.rope_rows.data_ptr(), a.data_ptr(), B,
+                                                             self.heads, self.hd, self.max_ctx, splits, ws, self._st()),
+                           "mxq_attn_decode_batch_kv8_f16")
+            else:
+                _lib.check(lib.mxq_attn_decode_batch_f16(y.data_ptr(), self.k_cache[i].data_ptr(), self.v_cache[i].data_ptr(),
+                                                         self.pos.data_ptr(), self.rope_rows.data_ptr(), a.data_ptr(), B, self.heads,
+                                                         self.hd, self.max_ctx, splits, ws, self._st()), "mxq_attn_decode_batch_f16")
             h = h + packing.linear(a, o)
             g = packing.linear(self._rms_rows(h), gu)
             act = torch.empty((B, self.inter), dtype=torch.float16, device=self.dev)
@@ -619,12 +662,26 @@ class BatchedDecodeStage(DecodeStage):
         self.slots.fill(b, T)
         try:
             if T:
-                h = self._prefill_layers(h, self.k_cache[:, b], self.v_cache[:, b], 0)
+                if self.kv_bits == 8:          # per layer: the slot's (codes, scales) pair of K and of V
+                    n = len(self.w)
+                    h = self._prefill_layers(h, [(self.k_codes[i, b], self.k_scale[i, b]) for i in range(n)],
+                                             [(self.v_codes[i, b], self.v_scale[i, b]) for i in range(n)], 0)
+                else:
+                    h = self._prefill_layers(h, self.k_cache[:, b], self.v_cache[:, b], 0)
         except BaseException:
             self.slots.release(b)              # (the device position was never set: the slot is still empty there)
             raise
         self.pos[b] = T
         return h
+
+    def _prefill_attn(self, lib, y, k_cache, v_cache, a, T: int, p0: int, st):
+        if self.kv_bits == 16:
+            return super()._prefill_attn(lib, y, k_cache, v_cache, a, T, p0, st)
+        (kc, ks), (vc, vs) = k_cache, v_cache
+        _lib.check(lib.mxq_attn_prefill_kv8_f16(y.data_ptr(), kc.data_ptr(), ks.data_ptr(), vc.data_ptr(), vs.data_ptr(),
+                                                self.cos.data_ptr(), self.sin.data_ptr(), a.data_ptr(), self._k_scratch.data_ptr(),
+                                                self._v_scratch.data_ptr(), T, p0, self.heads, self.hd, self.max_ctx, st),
+                   "mxq_attn_prefill_kv8_f16")
 
     def prefill_tokens_slot(self, b: int, ids):
         """Prompt ids (int64 [T], T >= 1) into the empty slot ``b`` -> the slot's first generated id (tensor [1])."""
@@ -644,8 +701,8 @@ class BatchedDecodeStage(DecodeStage):
     def reset(self):
         self.slots.reset()
         self.pos.fill_(-1)
-        self.k_cache.zero_()
-        self.v_cache.zero_()
+        for t in self._kv_tensors():
+            t.zero_()
 
     def seek_slot(self, b: int, position: int, seed: int = 5):
         """Benchmark helper: occupy the empty slot ``b`` as if ``position`` tokens had been decoded (seeded random cache rows)."""
@@ -653,8 +710,16 @@ class BatchedDecodeStage(DecodeStage):
             raise ValueError("position outside the KV cache")
         self.slots.fill(b, position)
         g = torch.Generator(device=self.dev).manual_seed(seed + b)
-        for c in (self.k_cache, self.v_cache):
-            c[:, b, :, :position].copy_(torch.randn(c[:, b, :, :position].shape, generator=g, device=self.dev).half())
+        if self.kv_bits == 8:
+            # random codes over the whole range and the scales of rows whose largest magnitude is 2.5 .. 3.5 (what the largest of
+            # 128 standard normal values comes to): the bytes and the arithmetic of a real cache, not its statistics
+            for codes, scale in ((self.k_codes, self.k_scale), (self.v_codes, self.v_scale)):
+                shape = codes[:, b, :, :position].shape
+                codes[:, b, :, :position].copy_(torch.randint(-127, 128, shape, generator=g, device=self.dev, dtype=torch.int8))
+                scale[:, b, :, :position].copy_((2.5 + torch.rand(shape[:-1], generator=g, device=self.dev)) / 127.0)
+        else:
+            for c in (self.k_cache, self.v_cache):
+                c[:, b, :, :position].copy_(torch.randn(c[:, b, :, :position].shape, generator=g, device=self.dev).half())
         self.pos[b] = position
 
     def capture_token_loop(self, token_buf: torch.Tensor):

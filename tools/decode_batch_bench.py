@@ -3,7 +3,11 @@
 model (32 layers), one GPU, both in this process on the same packed weights and alternating.  For every B and start position:
 HIP events around TOKENS graph replays after a warm-up run, two repeats.  Prints aggregate tokens/s, ms per step, the ratio
 to the batch-1 loop of the same repeat, launches per layer and packed-weight bytes per step over the step time.
-    python tools/decode_batch_bench.py [--out profiles/decode_batch_bench.txt] [--batches 1,2,4,8,16,32] [--layers 32]"""
+    python tools/decode_batch_bench.py [--out profiles/decode_batch_bench.txt] [--batches 1,2,4,8,16,32] [--layers 32]
+--kv-bits 8: the int8 KV cache (BatchedDecodeStage(kv_bits=8)) against the fp16 one instead -- the two captured batched token
+loops on the same packed weights, alternating, with the same replay counts and repeats, tokens/s of both and their ratio per B
+and start position; then the time of a 512-token prefill_slot in both modes (the int8 one includes the expand pass).
+    python tools/decode_batch_bench.py --kv-bits 8 [--out profiles/decode_kv8_bench.txt] [--batches 1,8,16,32]"""
 import argparse
 import os
 import sys
@@ -26,14 +30,87 @@ def timed(fn):
     return e0.elapsed_time(e1) / TOKENS          # ms per step
 
 
+PREFILL_TOKENS, PREFILL_RUNS = 512, 5
+
+
+def kv8_main(args, dev, say):
+    """fp16 against int8 KV cache: the two batched token loops per B and start position, then a 512-token prompt."""
+    batches, starts = [int(b) for b in args.batches.split(",")], [int(s) for s in args.starts.split(",")]
+    single = DecodeStage(range(args.layers), dev, max_ctx=MAX_CTX)          # (owns the packed weights both stages share)
+    say(f"decode_kv8_bench: {args.layers} layers, Llama-2-7B shapes, W2/4A16 mixed layout ({single.packed_bytes() / 1e9:.3f} GB packed "
+        f"per step), KV cache {MAX_CTX}, fp16 (256 B per row) against int8 codes + f32 row scale (132 B per row); {TOKENS} timed "
+        f"graph replays after {WARM} warm-up ones, {REPEATS} repeats, the fp16 and the int8 loop alternating")
+    say(f"device: {torch.cuda.get_device_name(0)}")
+    for B in batches:
+        stages = {bits: BatchedDecodeStage(range(args.layers), dev, batch=B, max_ctx=MAX_CTX, weights_of=single, kv_bits=bits)
+                  for bits in (16, 8)}
+        bufs = {bits: torch.zeros(B, dtype=torch.int64, device=dev) for bits in stages}
+        for bits, st in stages.items():
+            st.capture_token_loop(bufs[bits])
+
+        def run(bits, start, n):
+            st = stages[bits]
+            st.reset()
+            for b in range(B):
+                st.seek_slot(b, start)
+            return lambda: st.decode_tokens(bufs[bits], [1 + b for b in range(B)], n)
+
+        say(f"B {B:2d}: KV cache {stages[16].kv_cache_bytes() / 1e9:.2f} GB fp16, {stages[8].kv_cache_bytes() / 1e9:.2f} GB int8")
+        for start in starts:
+            for bits in (16, 8):
+                run(bits, start, WARM)()
+            ratios, rows = [], []
+            for _ in range(REPEATS):
+                ms16 = timed(run(16, start, TOKENS))
+                ms8 = timed(run(8, start, TOKENS))
+                ratios.append(ms16 / ms8)
+                rows.append((ms16, ms8))
+            mean = sum(ratios) / len(ratios)
+            spread = (max(ratios) - min(ratios)) / mean
+            for r, (ms16, ms8) in enumerate(rows):
+                say(f"B {B:2d} start {start:4d} repeat {r}: fp16 {B / ms16 * 1e3:8.1f} tokens/s aggregate, {ms16:7.3f} ms/step; int8 "
+                    f"{B / ms8 * 1e3:8.1f} tokens/s aggregate, {ms8:7.3f} ms/step; int8 / fp16 {ratios[r]:.3f}")
+            say(f"B {B:2d} start {start:4d}: int8 tokens/s over fp16 tokens/s {mean:.3f} (spread of the {REPEATS} repeats {spread * 100:.1f} %)")
+        if B == batches[-1]:
+            # a 512-token prompt into slot 0, HIP events around each run after one warm-up run, the two modes alternating
+            g = torch.Generator(device=dev).manual_seed(11)
+            prompt = (torch.randn(PREFILL_TOKENS, stages[16].hidden, generator=g, device=dev) * 0.02).half()
+            times = {16: [], 8: []}
+            for i in range(PREFILL_RUNS + 1):
+                for bits, st in stages.items():
+                    st.reset()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    e0.record()
+                    st.prefill_slot(0, prompt)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    if i:
+                        times[bits].append(e0.elapsed_time(e1))
+            for bits in (16, 8):
+                t = sorted(times[bits])
+                say(f"prefill_slot, {PREFILL_TOKENS} tokens, {args.layers} layers, kv_bits {bits:2d}: median {t[len(t) // 2]:.3f} ms "
+                    f"(min {t[0]:.3f}, max {t[-1]:.3f}; {PREFILL_RUNS} runs after a warm-up one"
+                    + ("; append + expand K + expand V + attention per layer)" if bits == 8 else "; append + attention per layer)"))
+        del stages, bufs
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                                   "decode_batch_bench.txt"))
-    ap.add_argument("--batches", default="1,2,4,8,16,32")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--batches", default=None)
     ap.add_argument("--starts", default="64,1920")
     ap.add_argument("--layers", type=int, default=32)
+    ap.add_argument("--kv-bits", type=int, default=16, choices=(16, 8),
+                    help="8: compare the int8 KV cache's batched loop with the fp16 one (profiles/decode_kv8_bench.txt)")
     args = ap.parse_args()
+    kv8 = args.kv_bits == 8
+    if args.out is None:
+        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                "decode_kv8_bench.txt" if kv8 else "decode_batch_bench.txt")
+    if args.batches is None:
+        args.batches = "1,8,16,32" if kv8 else "1,2,4,8,16,32"
     batches, starts = [int(b) for b in args.batches.split(",")], [int(s) for s in args.starts.split(",")]
     dev = torch.device("cuda:0")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
@@ -44,6 +121,10 @@ def main():
         out.write(line + "\n")
         out.flush()
 
+    if kv8:
+        kv8_main(args, dev, say)
+        out.close()
+        return
     single = DecodeStage(range(args.layers), dev, max_ctx=MAX_CTX)
     tb1 = torch.zeros(1, dtype=torch.int64, device=dev)
     single.capture_token_loop(tb1)
