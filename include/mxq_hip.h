@@ -622,6 +622,54 @@ int mxq_lmhead_argmax_f16(const void* h, const void* norm_w, float eps, const vo
 int mxq_lmhead_argmax_advance_f16(const void* h, const void* norm_w, float eps, const void* w, int V, int K, void* part,
                                   int part_slots, void* token, void* pos, void* generated, int max_generated, void* stream);
 
+/* ---- Sampling (csrc/sample.hip) ------------------------------------------------------------------------------------------
+ * mxq_sample_rows_f16: temperature, top-k, top-p and the draw of ONE token id per row of fp16 logits, all rows in one launch,
+ * one workgroup per row.  logits fp16 [rows, row_stride] (V logits per row; the columns beyond V are read in whole 16-byte
+ * chunks and ignored); temperature, top_p f32 [rows]; top_k i32 [rows]; seed, ctr, tokens i64 [rows]; every per-row argument is
+ * read from device memory by the kernel.  The result is defined exactly -- a token id is a function of the row's logits and its
+ * five parameters alone, and tests compare ids for equality with a numpy restatement (tests/sample_guard.py).
+ *
+ * THE DEFINITION, for one row l[0..V) with temperature T, top_k k, top_p p, seed and ctr' = ctr + ctr_offset (64-bit
+ * wrap-around); "logit values" compare as IEEE numbers, so -0 == +0:
+ *   fixed results, in this order:
+ *     ctr' < 0 (an empty slot)                   -> -1
+ *     every logit NaN                            -> 0
+ *     T == 0, or T outside [2^-10, 2^10] (NaN included), or the largest non-NaN logit is +inf or -inf
+ *                                                -> the lowest index of the largest non-NaN logit (mxq_lmhead_argmax_f16's rule)
+ *   weights are integers.  With m the largest non-NaN logit:
+ *     d = (float)m - (float)l[v]
+ *     c = 1.44269504f / T                        (IEEE fp32 division)
+ *     y = d * c
+ *     q[v] = 0                                   when !(y < 40.0f): NaN and -inf logits included
+ *     otherwise  i = (int)y,  f = y - (float)i,  x = -f
+ *       g = P(x) = (((((c6 x + c5) x + c4) x + c3) x + c2) x + c1) x + c0     plain fp32, every multiply and add rounded
+ *           c0 = 0x1.000000p+0f   c1 = 0x1.62e42cp-1f   c2 = 0x1.ebfabcp-3f   c3 = 0x1.c694ecp-5f
+ *           c4 = 0x1.39e9b0p-7f   c5 = 0x1.4e600cp-10f  c6 = 0x1.ca8f0ap-14f
+ *           (the degree-6 Chebyshev interpolant of 2^x on [-1, 0], |P(x) - 2^x| < 2e-8)
+ *       g = 1.0f when f == 0, else min(g, 1.0f)
+ *       mant = (uint32)(g * 16777216.0f)         (truncation)
+ *       q[v] = ((uint64)mant << 16) >> i
+ *     The largest logit weighs exactly 2^40; every sum below is an exact sum of 64-bit integers, whatever its order; V <= 2^20
+ *     keeps them below 2^60.  |q - 2^40 e^(-d/T)| <= 2^-16 * 2^40 e^(-d/T) + 1 over every fp16 difference and the whole
+ *     temperature range (tests/test_sample_cpu.py; the measured worst case is in profiles/sample_guard.txt).
+ *   top-k.  t_k = the k-th largest non-NaN logit value, counted with multiplicity; kept: l[v] >= t_k -- ties at the cut are all
+ *     kept.  k <= 0, or k >= the number of non-NaN logits: all non-NaN logits are kept.
+ *   top-p, applied to what top-k kept.  p >= 1 (or NaN): off.  Else p24 = (uint32)(p * 16777216.0f) (0 for p <= 0);
+ *     Z1 = the sum of q over the kept set; need = max((Z1 * p24) >> 24, 1), the product taken in 128 bits; t_p = the largest
+ *     logit value t whose kept mass {l[v] >= t} is >= need; kept: l[v] >= t_p -- ties are kept whole.
+ *   the draw.  x = word 0 of Philox4x32-10 (Salmon et al., SC'11) at counter (lo32(ctr'), hi32(ctr'), 0, 0) under the key
+ *     (lo32(seed), hi32(seed)); u24 = x >> 8; thr = (Z2 * u24) >> 24 with Z2 the kept mass (128-bit product); the token is the
+ *     smallest kept index whose inclusive prefix sum of q, in index order, exceeds thr.
+ * Because the logits are fp16, both cuts are found exactly: an order-preserving 16-bit key and two 256-bin histograms in LDS
+ * per cut (high byte, then low byte inside the bin of the cut), integer counts for top-k, 64-bit masses for top-p; the draw is a
+ * workgroup prefix scan of 64-bit integers.  There is no floating-point atomic and no floating-point sum.  The row is re-read
+ * from L2 in every pass, not staged.  Stream-ordered, allocates nothing, replays in a hipGraph; a repeated launch gives the
+ * same ids, and a row's id does not depend on the other rows.  Only tokens[0 .. rows) is written.
+ * Validation, before anything is launched: MXQ_E_NULL; MXQ_E_SHAPE for rows outside 1..65536, V outside 1..2^20, row_stride < V
+ * or row_stride % 8 != 0; MXQ_E_ALIGN: logits 16 bytes, temperature / top_k / top_p 4, seed / ctr / tokens 8. */
+int mxq_sample_rows_f16(const void* logits, int64_t row_stride, int rows, int V, const void* temperature, const void* top_k,
+                        const void* top_p, const void* seed, const void* ctr, int64_t ctr_offset, void* tokens, void* stream);
+
 /* MXAsymQuantizer.forward (utils_quant.py:316-462; 2-D, layerwise=False branch):
  * fake-quantise w[rows, cols] of `dtype` into out (same shape/dtype), bit-identical to
  * the reference in fp32 / bf16 / fp16.  cols % 64 == 0.

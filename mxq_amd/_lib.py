@@ -105,6 +105,7 @@ SIGNATURES = {
     "mxq_kv8_append_rope_f16": (c_int, [c_void_p] * 7 + [c_int] * 5 + [c_void_p]),
     "mxq_kv8_expand_f16": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),
     "mxq_attn_prefill_kv8_f16": (c_int, [c_void_p] * 10 + [c_int] * 5 + [c_void_p]),
+    "mxq_sample_rows_f16": (c_int, [c_void_p, c_int64, c_int, c_int] + [c_void_p] * 5 + [c_int64, c_void_p, c_void_p]),
     "mxq_fakequant_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "mxq_fakequant_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_int, c_void_p]),
     "mxq_gemv_awq_f16": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_void_p]),

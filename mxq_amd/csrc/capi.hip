@@ -373,6 +373,18 @@ int mxq_lmhead_argmax_advance_f16(const void* h, const void* norm_w, float eps, 
                                         (hipStream_t)stream);
 }
 
+// sampling (csrc/sample.hip): the logits are read 16 bytes at a time, the per-row arrays by their element size
+int mxq_sample_rows_f16(const void* logits, int64_t row_stride, int rows, int V, const void* temperature, const void* top_k,
+                        const void* top_p, const void* seed, const void* ctr, int64_t ctr_offset, void* tokens, void* stream) {
+    if (!logits || !temperature || !top_k || !top_p || !seed || !ctr || !tokens) return MXQ_E_NULL;
+    if (rows < 1 || rows > 65536 || V < 1 || V > (1 << 20) || row_stride < V || row_stride % 8 != 0) return MXQ_E_SHAPE;
+    if (!aligned16(logits) || !aligned4(temperature) || !aligned4(top_k) || !aligned4(top_p) || ((uintptr_t)seed & 7) ||
+        ((uintptr_t)ctr & 7) || ((uintptr_t)tokens & 7))
+        return MXQ_E_ALIGN;
+    return mxq_launch_sample_rows_f16(logits, row_stride, rows, V, temperature, top_k, top_p, seed, ctr, ctr_offset, tokens,
+                                      (hipStream_t)stream);
+}
+
 // ---- uniform layouts of the config-5 sweep ---------------------------------------------------
 
 size_t mxq_qweight_bytes_layout(int N, int K, int layout) {

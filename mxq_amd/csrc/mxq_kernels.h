@@ -214,6 +214,10 @@ int mxq_launch_kv8_append_rope_f16(const void* qkv, void* k_codes, void* k_scale
                                    const void* sin_t, int tokens, int pos0, int heads, int max_ctx, hipStream_t stream);
 int mxq_launch_kv8_expand_f16(const void* codes, const void* scale, void* out16, int rows, int heads, int max_ctx,
                               hipStream_t stream);
+// csrc/sample.hip: one sampled token per row of fp16 logits (include/mxq_hip.h, "Sampling"); one workgroup per row
+int mxq_launch_sample_rows_f16(const void* logits, int64_t row_stride, int rows, int V, const void* temperature, const void* top_k,
+                               const void* top_p, const void* seed, const void* ctr, int64_t ctr_offset, void* tokens,
+                               hipStream_t stream);
 int mxq_launch_fakequant_fwd(const void* w, void* out, int rows, int cols, int num_bits, int dtype,
                              hipStream_t stream);
 int mxq_launch_fakequant_bwd(const void* grad_out, const void* w, void* grad_in, int64_t n, float lo, float hi,

@@ -20,6 +20,7 @@ import torch
 from . import _lib
 from . import llama_shapes as LS
 from . import packing
+from . import sampling as _sampling
 
 
 _concat_packed = packing.concat_packed
@@ -552,6 +553,13 @@ class BatchedDecodeStage(DecodeStage):
         self._h_in = torch.zeros(batch, hidden, device=dev, dtype=torch.float16)
         self._h_out = None
         self._tgraph = self._tgraph_long = None
+        # per-slot sampling parameters, read by mxq_sample_rows_f16 from device memory (a captured loop sees a slot's new
+        # request without a re-capture); ``sampling`` their host mirror.  Every slot starts greedy with seed 0
+        self.samp_temperature = torch.zeros(batch, dtype=torch.float32, device=dev)
+        self.samp_top_k = torch.zeros(batch, dtype=torch.int32, device=dev)
+        self.samp_top_p = torch.ones(batch, dtype=torch.float32, device=dev)
+        self.samp_seed = torch.zeros(batch, dtype=torch.int64, device=dev)
+        self.sampling = [_sampling.GREEDY] * batch
 
     def _cache_shape(self, n_layers: int):
         return (n_layers, self.batch, self.heads, self.max_ctx, self.hd)
@@ -604,8 +612,37 @@ class BatchedDecodeStage(DecodeStage):
     def embed_token(self, tok):
         return self.embed.index_select(0, tok.clamp(0, self.embed.shape[0] - 1))      # (an empty slot's id is -1)
 
-    def head(self, h, out: Optional[torch.Tensor] = None):
-        """Final RMSNorm (mxq_rmsnorm_rows_f16) + lm_head (``F.linear``) + greedy argmax -> ids int64 [rows]."""
+    def set_sampling(self, b: int, params: Optional[_sampling.SamplingParams]):
+        """The sampling parameters of slot ``b`` (None: greedy, seed 0), for its next ``head(sample=True)`` / sampled graph
+        replay on.  A request's stream depends only on (seed, cache position): not on the slot, not on the other slots."""
+        self.slots._slot(b)
+        params = _sampling.GREEDY if params is None else params
+        if not isinstance(params, _sampling.SamplingParams):
+            raise TypeError(f"set_sampling takes a SamplingParams, got {type(params).__name__}")
+        if params == self.sampling[b]:
+            return
+        self.samp_temperature[b] = float(params.temperature)
+        self.samp_top_k[b] = int(params.top_k)
+        self.samp_top_p[b] = float(params.top_p)
+        self.samp_seed[b] = params.seed_i64
+        self.sampling[b] = params
+
+    def _sample(self, h, sl: slice, ctr_offset: int, out: Optional[torch.Tensor] = None):
+        """RMSNorm rows + lm_head (``F.linear``) + mxq_sample_rows_f16 on the parameters and positions of the slots ``sl``."""
+        logits = torch.nn.functional.linear(self._rms_rows(h.contiguous()), self.lm_head)
+        return _sampling.sample_rows(logits, self.samp_temperature[sl], self.samp_top_k[sl], self.samp_top_p[sl], self.samp_seed[sl],
+                                     self.pos[sl], ctr_offset, out)
+
+    def head(self, h, out: Optional[torch.Tensor] = None, sample: bool = False, ctr_offset: int = 0):
+        """Final RMSNorm (mxq_rmsnorm_rows_f16) + lm_head (``F.linear``) + greedy argmax -> ids int64 [rows].
+        ``sample``: h is [batch, hidden] and the last step is mxq_sample_rows_f16 (include/mxq_hip.h, "Sampling") on every
+        slot's own parameters (``set_sampling``) with the counter ``pos + ctr_offset`` -- before ``advance``, ``pos`` is the cache
+        position of the row that produced the logits; an empty slot's id is -1, a slot at temperature 0 gets the greedy id.
+        ``out`` (int64 [batch], contiguous) is written by the launch itself."""
+        if sample:
+            if h.shape[0] != self.batch:
+                raise ValueError(f"head(sample=True) takes [{self.batch}, {self.hidden}] rows, one per slot")
+            return self._sample(h, slice(0, self.batch), ctr_offset, out)
         ids = torch.nn.functional.linear(self._rms_rows(h.contiguous()), self.lm_head).argmax(dim=-1)
         return ids if out is None else out.copy_(ids)
 
@@ -683,24 +720,35 @@ class BatchedDecodeStage(DecodeStage):
                                                 self._v_scratch.data_ptr(), T, p0, self.heads, self.hd, self.max_ctx, st),
                    "mxq_attn_prefill_kv8_f16")
 
-    def prefill_tokens_slot(self, b: int, ids):
-        """Prompt ids (int64 [T], T >= 1) into the empty slot ``b`` -> the slot's first generated id (tensor [1])."""
+    def prefill_tokens_slot(self, b: int, ids, sampling: Optional[_sampling.SamplingParams] = None):
+        """Prompt ids (int64 [T], T >= 1) into the empty slot ``b`` -> the slot's first generated id (tensor [1]).
+        ``sampling``: the request's parameters (``set_sampling``; None leaves the slot's as they are -- greedy after a
+        ``release``).  A slot that is not greedy draws its first id too, at counter T - 1: the cache position of the prompt's
+        last row, as every later id is drawn at the position of the row that produced its logits."""
         if getattr(self, "embed", None) is None or getattr(self, "lm_head", None) is None:
             raise ValueError("prefill_tokens_slot needs the first and the last stage in one process")
         ids = torch.as_tensor(ids, dtype=torch.int64, device=self.dev).reshape(-1)
         if ids.numel() == 0:
             raise ValueError("prefill_tokens_slot needs at least one prompt token")
         h = self.prefill_slot(b, self.embed_token(ids))
+        if sampling is not None:
+            self.set_sampling(b, sampling)
+        if self.sampling[b].temperature != 0:
+            return self._sample(h[-1:], slice(b, b + 1), -1)
         return self.head(h[-1:]).reshape(-1)[:1]
 
     def release(self, b: int):
-        """Free slot ``b``: its position becomes -1; its cache rows are left as they are (the next prompt overwrites them)."""
+        """Free slot ``b``: its position becomes -1; its cache rows are left as they are (the next prompt overwrites them); its
+        sampling parameters go back to greedy."""
         self.slots.release(b)
         self.pos[b] = -1
+        self.set_sampling(b, None)
 
     def reset(self):
         self.slots.reset()
         self.pos.fill_(-1)
+        for b in range(self.batch):
+            self.set_sampling(b, None)
         for t in self._kv_tensors():
             t.zero_()
 
@@ -722,10 +770,14 @@ class BatchedDecodeStage(DecodeStage):
                 c[:, b, :, :position].copy_(torch.randn(c[:, b, :, :position].shape, generator=g, device=self.dev).half())
         self.pos[b] = position
 
-    def capture_token_loop(self, token_buf: torch.Tensor):
+    def capture_token_loop(self, token_buf: torch.Tensor, sample: bool = False):
         """Capture ids -> embedding + rotary rows -> layers -> final norm + lm_head + argmax -> ids -> advance as the short /
         long pair of hipGraphs, updating ``token_buf`` (int64 [batch], -1 in the columns of empty slots) in place.  Call it
-        while every slot is empty: the warm-up runs write the first cache rows of every slot and overwrite ``token_buf``."""
+        while every slot is empty: the warm-up runs write the first cache rows of every slot and overwrite ``token_buf``.
+        ``sample``: the loop ends in mxq_sample_rows_f16 instead of the argmax (``head(sample=True)``; the launch writes
+        ``token_buf`` itself, -1 for empty slots included); the graphs read every slot's parameters from device memory, so
+        ``set_sampling`` / ``prefill_tokens_slot(sampling=...)`` between replays need no re-capture.  ``decode_tokens`` replays
+        whichever loop was captured last."""
         if getattr(self, "embed", None) is None or getattr(self, "lm_head", None) is None:
             raise ValueError("capture_token_loop needs the first and the last stage in one process")
         if token_buf.dtype != torch.int64 or token_buf.shape != (self.batch,) or not token_buf.is_contiguous():
@@ -735,8 +787,11 @@ class BatchedDecodeStage(DecodeStage):
 
         def one():
             self._gather_rows(token_buf)
-            ids = self.head(self.step(self._h_in, rope_done=True))
-            token_buf.copy_(torch.where(self.pos >= 0, ids, -1))
+            if sample:
+                self.head(self.step(self._h_in, rope_done=True), out=token_buf, sample=True)
+            else:
+                ids = self.head(self.step(self._h_in, rope_done=True))
+                token_buf.copy_(torch.where(self.pos >= 0, ids, -1))
             self._advance_device()
         self.pos.zero_()                       # warm-up on real positions (the host mirror stays empty: nothing is reserved)
         for _ in range(2):

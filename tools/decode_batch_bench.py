@@ -7,7 +7,12 @@ to the batch-1 loop of the same repeat, launches per layer and packed-weight byt
 --kv-bits 8: the int8 KV cache (BatchedDecodeStage(kv_bits=8)) against the fp16 one instead -- the two captured batched token
 loops on the same packed weights, alternating, with the same replay counts and repeats, tokens/s of both and their ratio per B
 and start position; then the time of a 512-token prefill_slot in both modes (the int8 one includes the expand pass).
-    python tools/decode_batch_bench.py --kv-bits 8 [--out profiles/decode_kv8_bench.txt] [--batches 1,8,16,32]"""
+    python tools/decode_batch_bench.py --kv-bits 8 [--out profiles/decode_kv8_bench.txt] [--batches 1,8,16,32]
+--sample: the SAMPLED captured loop (capture_token_loop(sample=True); every slot at T = 0.8, top-k 50, top-p 0.9, its own seed)
+against the greedy one -- two batched stages on the same packed weights, alternating, same replay counts and repeats; then
+mxq_sample_rows_f16 alone at V = 32000 and B = 1 / 8 / 32 / 256 against the torch chain (softmax, topk, sort, cumsum,
+multinomial) and against the three launches it replaces in the loop (argmax, where, copy), HIP events around CALLS calls.
+    python tools/decode_batch_bench.py --sample [--out profiles/sample_bench.txt] [--batches 1,8,32]"""
 import argparse
 import os
 import sys
@@ -96,6 +101,117 @@ def kv8_main(args, dev, say):
         torch.cuda.empty_cache()
 
 
+CALLS, CALL_WARM, CALL_REPEATS = 200, 20, 3
+SAMPLE_T, SAMPLE_K, SAMPLE_P = 0.8, 50, 0.9
+
+
+def per_call_us(fn, graph=False):
+    """Median over CALL_REPEATS of (HIP events around CALLS calls) / CALLS, after CALL_WARM calls; us.  ``graph``: the CALLS
+    calls are captured once and replayed -- the GPU's time per call without what the host needs to issue it."""
+    for _ in range(CALL_WARM):
+        fn()
+    many = lambda: [fn() for _ in range(CALLS)]
+    if graph:
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            many()
+        many = g.replay
+        many()
+    us = []
+    for _ in range(CALL_REPEATS):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        many()
+        e1.record()
+        torch.cuda.synchronize()
+        us.append(e0.elapsed_time(e1) / CALLS * 1e3)
+    return sorted(us)[len(us) // 2], min(us), max(us)
+
+
+def torch_chain(logits, gen):
+    """The torch route to the same distribution: temperature softmax, top-k (ties kept), nucleus cut on the sorted
+    probabilities, multinomial draw -> ids [rows, 1]."""
+    probs = torch.softmax(logits.float() / SAMPLE_T, dim=-1)
+    kth = torch.topk(probs, SAMPLE_K, dim=-1).values[:, -1:]
+    probs = torch.where(probs < kth, 0.0, probs)
+    sp, si = torch.sort(probs, dim=-1, descending=True)
+    cs = sp.cumsum(dim=-1)
+    sp = torch.where(cs - sp >= SAMPLE_P * cs[:, -1:], 0.0, sp)
+    return si.gather(-1, torch.multinomial(sp, 1, generator=gen))
+
+
+def sample_main(args, dev, say):
+    from mxq_amd.sampling import SamplingParams, sample_rows
+    batches, starts = [int(b) for b in args.batches.split(",") if b], [int(s) for s in args.starts.split(",")]
+    single = DecodeStage(range(args.layers if batches else 1), dev, max_ctx=MAX_CTX)      # (owns the packed weights both stages share)
+    say(f"sample_bench: {args.layers} layers, Llama-2-7B shapes, W2/4A16 mixed layout ({single.packed_bytes() / 1e9:.3f} GB packed per "
+        f"step), KV cache {MAX_CTX} fp16, vocab {single.lm_head.shape[0]}; the greedy captured loop (F.linear + argmax + where + copy) "
+        f"against the sampled one (F.linear + mxq_sample_rows_f16; every slot T {SAMPLE_T}, top-k {SAMPLE_K}, top-p {SAMPLE_P}, seed = "
+        f"slot); {TOKENS} timed graph replays after {WARM} warm-up ones, {REPEATS} repeats, the two loops alternating")
+    say(f"device: {torch.cuda.get_device_name(0)}" + ("; the sampled stage allocated and captured first" if args.sampled_first else ""))
+    for B in batches:
+        # (--sampled-first: a control -- the two stages' caches change places in the allocator)
+        stages = {mode: BatchedDecodeStage(range(args.layers), dev, batch=B, max_ctx=MAX_CTX, weights_of=single)
+                  for mode in (("sampled", "greedy") if args.sampled_first else ("greedy", "sampled"))}
+        bufs = {mode: torch.zeros(B, dtype=torch.int64, device=dev) for mode in stages}
+        for mode, st in stages.items():
+            st.capture_token_loop(bufs[mode], sample=mode == "sampled")
+
+        def run(mode, start, n):
+            st = stages[mode]
+            st.reset()
+            for b in range(B):
+                st.seek_slot(b, start)
+                if mode == "sampled":
+                    st.set_sampling(b, SamplingParams(SAMPLE_T, SAMPLE_K, SAMPLE_P, seed=b))
+            return lambda: st.decode_tokens(bufs[mode], [1 + b for b in range(B)], n)
+
+        for start in starts:
+            for mode in stages:
+                run(mode, start, WARM)()
+            ratios, rows = [], []
+            for _ in range(REPEATS):
+                msg = timed(run("greedy", start, TOKENS))
+                mss = timed(run("sampled", start, TOKENS))
+                ratios.append(msg / mss)
+                rows.append((msg, mss))
+            mean = sum(ratios) / len(ratios)
+            spread = (max(ratios) - min(ratios)) / mean
+            for r, (msg, mss) in enumerate(rows):
+                say(f"B {B:2d} start {start:4d} repeat {r}: greedy {B / msg * 1e3:8.1f} tokens/s aggregate, {msg:7.3f} ms/step; sampled "
+                    f"{B / mss * 1e3:8.1f} tokens/s aggregate, {mss:7.3f} ms/step; sampled / greedy {ratios[r]:.3f}; "
+                    f"sampled - greedy {(mss - msg) * 1e3:+7.1f} us/step")
+            say(f"B {B:2d} start {start:4d}: sampled tokens/s over greedy tokens/s {mean:.3f} (spread of the {REPEATS} repeats {spread * 100:.1f} %)")
+        del stages, bufs
+        torch.cuda.empty_cache()
+    if args.no_per_call:
+        return
+    # the launch alone, eager, on N(0, 3^2) logits (about as peaked as a trained model's), against what it replaces
+    V = single.lm_head.shape[0]
+    say(f"per call at V = {V}: median (min .. max) of {CALL_REPEATS} x (HIP events around {CALLS} calls) after {CALL_WARM} warm-up calls, "
+        f"us; 'eager' includes what the host needs to issue a call where that exceeds the GPU time, 'in a graph' is one replay of {CALLS} "
+        "captured calls: the GPU time alone")
+    for rows in (1, 8, 32, 256):
+        g = torch.Generator(device=dev).manual_seed(rows)
+        logits = (torch.randn(rows, V, generator=g, device=dev) * 3).half()
+        f = lambda v, d: torch.full((rows,), v, dtype=d, device=dev)
+        temperature, top_k, top_p, seed = f(SAMPLE_T, torch.float32), f(SAMPLE_K, torch.int32), f(SAMPLE_P, torch.float32), torch.arange(rows, device=dev)
+        ctr, out, pos = torch.arange(rows, device=dev) + 64, torch.empty(rows, dtype=torch.int64, device=dev), torch.zeros(rows, dtype=torch.int64, device=dev)
+        k0, p1 = f(0, torch.int32), f(1.0, torch.float32)
+        calls = {"T + top-k + top-p": lambda: sample_rows(logits, temperature, top_k, top_p, seed, ctr, 0, out),
+                 "temperature only": lambda: sample_rows(logits, temperature, k0, p1, seed, ctr, 0, out),
+                 "argmax + where + copy": lambda: out.copy_(torch.where(pos >= 0, logits.argmax(dim=-1), -1))}
+        fmt = lambda t: f"{t[0]:7.1f} ({t[1]:.1f} .. {t[2]:.1f})"
+        for name, fn in calls.items():
+            say(f"rows {rows:3d}: {'mxq_sample_rows_f16 ' if 'argmax' not in name else ''}{name}: eager {fmt(per_call_us(fn))}, in a graph "
+                f"{fmt(per_call_us(fn, graph=True))}")
+        chain, full = per_call_us(lambda: torch_chain(logits, g)), per_call_us(calls["T + top-k + top-p"])
+        say(f"rows {rows:3d}: torch chain (softmax, topk, where, sort, cumsum, where, multinomial, gather): eager {fmt(chain)}, "
+            f"{chain[0] / full[0]:.1f} x the eager sampler")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -104,14 +220,17 @@ def main():
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--kv-bits", type=int, default=16, choices=(16, 8),
                     help="8: compare the int8 KV cache's batched loop with the fp16 one (profiles/decode_kv8_bench.txt)")
+    ap.add_argument("--sample", action="store_true",
+                    help="compare the sampled captured loop with the greedy one, and time the sampler alone (profiles/sample_bench.txt)")
+    ap.add_argument("--sampled-first", action="store_true", help="with --sample: allocate and capture the sampled stage first")
+    ap.add_argument("--no-per-call", action="store_true", help="with --sample: skip the per-call timings")
     args = ap.parse_args()
     kv8 = args.kv_bits == 8
     if args.out is None:
         args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                "decode_kv8_bench.txt" if kv8 else "decode_batch_bench.txt")
+                                "sample_bench.txt" if args.sample else "decode_kv8_bench.txt" if kv8 else "decode_batch_bench.txt")
     if args.batches is None:
-        args.batches = "1,8,16,32" if kv8 else "1,2,4,8,16,32"
-    batches, starts = [int(b) for b in args.batches.split(",")], [int(s) for s in args.starts.split(",")]
+        args.batches = "1,8,32" if args.sample else "1,8,16,32" if kv8 else "1,2,4,8,16,32"
     dev = torch.device("cuda:0")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     out = open(args.out, "w")
@@ -121,10 +240,15 @@ def main():
         out.write(line + "\n")
         out.flush()
 
+    if args.sample:
+        sample_main(args, dev, say)
+        out.close()
+        return
     if kv8:
         kv8_main(args, dev, say)
         out.close()
         return
+    batches, starts = [int(b) for b in args.batches.split(",")], [int(s) for s in args.starts.split(",")]
     single = DecodeStage(range(args.layers), dev, max_ctx=MAX_CTX)
     tb1 = torch.zeros(1, dtype=torch.int64, device=dev)
     single.capture_token_loop(tb1)
