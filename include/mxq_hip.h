@@ -554,6 +554,61 @@ int mxq_kv_append_rope_f16(const void* qkv, void* k_cache, void* v_cache, const 
 int mxq_attn_prefill_f16(const void* qkv, void* k_cache, void* v_cache, const void* cos_t, const void* sin_t, void* out,
                          int tokens, int pos0, int heads, int head_dim, int max_ctx, void* stream);
 
+/* ---- Grouped-query attention (csrc/attn_gqa.hip, csrc/attn_prefill.hip; no reference counterpart) ------------------------
+ * `heads` query heads share `kv_heads` key / value heads: heads % kv_heads == 0, group size G = heads / kv_heads, 1 <= G <= 16,
+ * any integer (7 and 5 occur).  Query head h uses K/V head h / G -- the order of HF transformers' repeat_kv, which expands K/V
+ * head g into the query heads g*G .. g*G + G - 1.  Head dim 128.
+ * LAYOUTS.  qkv row: fp16 [(heads + 2*kv_heads) * 128] = q[heads*128] | k[kv_heads*128] | v[kv_heads*128], the fused projection's
+ * output with N = hidden + 2*kv_heads*128.  Caches: fp16 [kv_heads][max_ctx][128] per slot, batched with a leading [batch]
+ * dimension as above.  out: fp16 [heads*128] per row.  With kv_heads == heads all of them are the multi-head layouts above.
+ *
+ * mxq_attn_decode_batch_gqa_f16 mirrors mxq_attn_decode_batch_f16 slot by slot: pos int64 [batch] (device), rope_rows f32
+ * [batch][128], batch 1..256, splits 1..16;
+ *   pos[b] < 0: an EMPTY slot -- its out row is all zero, nothing of its cache is read into a result or written;
+ *   pos[b] >= max_ctx: refused -- the out row is all NaN, nothing is written to the cache;
+ * both uniform over a workgroup, decided before any barrier, neither touches the workspace.  Everything, positions included, is
+ * read from device memory: no allocation, no host synchronisation, hipGraph-replayable.
+ * kv_heads == heads (G = 1): the entry forwards to mxq_attn_decode_batch_f16's launch, the workspace size is
+ * mxq_attn_batch_workspace_bytes; out and both caches are that entry's bit for bit.
+ * G > 1: one workgroup per (slot, K/V head, split), grid kv_heads x splits x batch.  The keys 0 .. pos[b] are partitioned over the
+ * splits by the rule of mxq_attn_decode_split_f16 (units of 64 keys, trailing splits empty) at EVERY length: one algorithm, no
+ * short-context switch.  Inside a workgroup four waves divide the split's keys in whole 32-key tiles; each wave runs
+ * mxq_attn_prefill_f16's tile loop on v_mfma_f32_16x16x32_f16 with the G rotated query heads of the group in the MFMA columns
+ * 0 .. G - 1 (columns G .. 15 are zero operands; their results are never stored or merged).  The waves' {O[G][128], m[G], l[G]}
+ * are merged in LDS in fp32, in wave order.  A workgroup that is not the only key-holding split parks its part in the workspace;
+ * the (slot, K/V head)'s last arriver merges the parts in fp32 in split order whatever the arrival order (arrival counters
+ * zeroed once by the caller and left zeroed by the kernel; nobody waits).  The split that holds key pos[b] rotates the token's own
+ * key, stores the K and V rows at row pos[b] and takes them into the attention from on-chip memory as the fp16 values just
+ * stored; no other workgroup touches that row.  Each K and each V row of a (slot, K/V head) is loaded from memory ONCE per launch,
+ * not once per query head.  No LDS carve depends on max_ctx.
+ * Rounding points (mxq_attn_prefill_f16's): q rotated in fp32 and rounded once to fp16; the appended key is BIT-IDENTICAL to the
+ * row mxq_attn_decode_row_f16 / mxq_kv_append_rope_f16 append for the same K row and position (same expression, no contraction);
+ * values are copied; scores: fp32 accumulation times rsqrtf(128), NOT rounded to fp16; online softmax with fp32 m and l and
+ * __expf; l adds the fp32 probability BEFORE that probability is rounded once to fp16 as the P.V operand; O in fp32, the wave and
+ * split merges in fp32, O / l rounded once to fp16.  Deterministic: no floating-point atomics; a repeated launch is bit-identical.
+ * workspace (nullable when splits == 1): mxq_attn_gqa_workspace_bytes(batch, heads, kv_heads, splits) bytes = one counter per
+ * (slot, K/V head) in a head of 1024 * ceil(batch*kv_heads / 256) bytes, then {o[G][128], m[G], l[G]} f32 per (slot, K/V head,
+ * split); 0 for arguments the entry would refuse.
+ *
+ * mxq_kv_append_rope_gqa_f16: mxq_kv_append_rope_f16 over the kv_heads heads of a grouped qkv row [tokens, (heads + 2*kv_heads)*128].
+ * mxq_attn_prefill_gqa_f16: that append, then mxq_attn_prefill_f16's causal MFMA kernel in which query head h reads K/V head
+ * h / G (heads stay on the x grid, so a group's G workgroups are adjacent and share their K/V tiles through L2).  Every out row is
+ * BIT-IDENTICAL to the row mxq_attn_prefill_f16 computes on the repeat_kv-expanded problem, and the appended rows of K/V head g
+ * to those of expanded head g*G.
+ * Validation, before anything is launched: MXQ_E_NULL for a NULL operand (the workspace excepted as above); MXQ_E_SHAPE for batch
+ * outside 1..256, heads <= 0, kv_heads <= 0, heads % kv_heads != 0, heads / kv_heads > 16, head_dim != 128, max_ctx <= 0 or
+ * > 32768, splits outside 1..16, splits > 1 without a workspace, tokens <= 0, pos0 < 0, pos0 + tokens > max_ctx; MXQ_E_ALIGN:
+ * qkv, both caches, out and the workspace 16 bytes, pos 8, the tables and the rotary rows 4.  The decode entry's qkv and out
+ * need 16 bytes here, not 2 as mxq_attn_decode_batch_f16's: the MFMA operands are fetched with 16-byte vector loads. */
+size_t mxq_attn_gqa_workspace_bytes(int batch, int heads, int kv_heads, int splits);
+int mxq_attn_decode_batch_gqa_f16(const void* qkv, void* k_cache, void* v_cache, const void* pos, const void* rope_rows,
+                                  void* out, int batch, int heads, int kv_heads, int head_dim, int max_ctx, int splits,
+                                  void* workspace, void* stream);
+int mxq_kv_append_rope_gqa_f16(const void* qkv, void* k_cache, void* v_cache, const void* cos_t, const void* sin_t,
+                               int tokens, int pos0, int heads, int kv_heads, int head_dim, int max_ctx, void* stream);
+int mxq_attn_prefill_gqa_f16(const void* qkv, void* k_cache, void* v_cache, const void* cos_t, const void* sin_t, void* out,
+                             int tokens, int pos0, int heads, int kv_heads, int head_dim, int max_ctx, void* stream);
+
 /* Int8 KV cache (csrc/attn_kv8.hip): the STORED form of the caches above for the batched decode path.
  * THE FORMAT.  Per slot and layer, for K and V each: codes int8 [heads][max_ctx][128], two's complement; scale f32
  * [heads][max_ctx]; batched, both carry a leading [batch] dimension as the fp16 caches do.  A row costs 132 bytes against 256.

@@ -101,6 +101,10 @@ SIGNATURES = {
     "mxq_swiglu_rows_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "mxq_kv_append_rope_f16": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p]),
     "mxq_attn_prefill_f16": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
+    "mxq_attn_gqa_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "mxq_attn_decode_batch_gqa_f16": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_void_p, c_void_p]),
+    "mxq_kv_append_rope_gqa_f16": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_void_p]),
+    "mxq_attn_prefill_gqa_f16": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_void_p]),
     "mxq_attn_decode_batch_kv8_f16": (c_int, [c_void_p] * 8 + [c_int] * 5 + [c_void_p, c_void_p]),
     "mxq_kv8_append_rope_f16": (c_int, [c_void_p] * 7 + [c_int] * 5 + [c_void_p]),
     "mxq_kv8_expand_f16": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),

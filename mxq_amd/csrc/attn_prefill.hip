@@ -22,6 +22,9 @@
 //                                                that same permuted order;
 //                              and at the end O / l in fp32, rounded once to fp16.
 //
+// Both kernels take the qkv row's stride and, A, the offsets of K and V in it, B, the group size G: query head h reads K/V head
+// h / G (include/mxq_hip.h, "Grouped-query attention").  The multi-head entries pass (3 * hidden, hidden, 2 * hidden) and G = 1.
+//
 // Rows of the caches at and beyond pos0 + tokens may hold anything, NaN included: a tile row at or beyond the block's last
 // visible key is staged as ZERO without being loaded (0 * NaN in P.V would otherwise reach every query of the tile), which
 // also keeps every load inside the cache.  A row is never fully masked: key pos0 + t is the query's own, and key 0 is
@@ -51,14 +54,13 @@ static_assert(BQ == 16 * (PF_THREADS / 64) && BK == 64 && PF_THREADS == 4 * BK, 
 __global__ __launch_bounds__(256) void kv_append_rope_kernel(const uint16_t* __restrict__ qkv, uint16_t* __restrict__ k_cache,
                                                              uint16_t* __restrict__ v_cache, const float* __restrict__ cos_t,
                                                              const float* __restrict__ sin_t, int tokens, int pos0, int heads,
-                                                             int max_ctx) {
+                                                             int max_ctx, int64_t row_halfs, int64_t k_off, int64_t v_off) {
     const int idx = (int)blockIdx.x * 256 + (int)threadIdx.x;      // grid: x over heads * 8 threads, y = token
     const int c8 = idx & 7, h = idx >> 3, t = blockIdx.y;
     if (h >= heads) return;
-    const int64_t hidden = (int64_t)heads * HD;
     const int pos = pos0 + t;
-    const uint16_t* kh = qkv + (int64_t)t * 3 * hidden + hidden + (int64_t)h * HD;
-    const uint16_t* vh = kh + hidden;
+    const uint16_t* kh = qkv + (int64_t)t * row_halfs + k_off + (int64_t)h * HD;
+    const uint16_t* vh = qkv + (int64_t)t * row_halfs + v_off + (int64_t)h * HD;
     const uint4 k1w = *(const uint4*)(kh + c8 * 8), k2w = *(const uint4*)(kh + HD / 2 + c8 * 8);
     const uint4 v1w = *(const uint4*)(vh + c8 * 8), v2w = *(const uint4*)(vh + HD / 2 + c8 * 8);
     const float* cr = cos_t + (int64_t)pos * (HD / 2) + c8 * 8;
@@ -90,7 +92,7 @@ __global__ __launch_bounds__(PF_THREADS) void attn_prefill_kernel(const uint16_t
                                                                   const uint16_t* __restrict__ v_cache,
                                                                   const float* __restrict__ cos_t, const float* __restrict__ sin_t,
                                                                   uint16_t* __restrict__ out, int tokens, int pos0, int heads,
-                                                                  int max_ctx) {
+                                                                  int max_ctx, int64_t row_halfs, int G) {
     __shared__ __attribute__((aligned(16))) unsigned char k_s[2 * KHALF_BYTES];     // K tile: dims 0..63 | 64..127, swizzled rows
     __shared__ __attribute__((aligned(16))) uint16_t vt_s[HD * VT_STRIDE];          // V tile transposed: [dim][key]
     const int tid = threadIdx.x, wave = tid >> 6;
@@ -103,8 +105,8 @@ __global__ __launch_bounds__(PF_THREADS) void attn_prefill_kernel(const uint16_t
     const int t = q0 + wave * 16 + qi;                              // this lane's query (the MFMA column)
     const bool live = t < tokens;
     const int qpos = pos0 + t;
-    const uint16_t* kc = k_cache + (int64_t)h * max_ctx * HD;
-    const uint16_t* vc = v_cache + (int64_t)h * max_ctx * HD;
+    const uint16_t* kc = k_cache + (int64_t)(h / G) * max_ctx * HD;     // query head h reads K/V head h / G (G = 1: its own)
+    const uint16_t* vc = v_cache + (int64_t)(h / G) * max_ctx * HD;
 
     // q16 of the lane's query as the B operand of S^T = K . Q^T: element j of step s is dim 32 s + 8 g + j
     half8 qr[4];
@@ -113,7 +115,7 @@ __global__ __launch_bounds__(PF_THREADS) void attn_prefill_kernel(const uint16_t
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             raw[s] = (half8)(_Float16)0;
-            if (live) raw[s] = *(const half8*)(qkv + (int64_t)t * 3 * hidden + (int64_t)h * HD + 32 * s + 8 * g);
+            if (live) raw[s] = *(const half8*)(qkv + (int64_t)t * row_halfs + (int64_t)h * HD + 32 * s + 8 * g);
         }
 #pragma unroll
         for (int s = 0; s < 2; ++s)
@@ -248,20 +250,34 @@ __global__ __launch_bounds__(PF_THREADS) void attn_prefill_kernel(const uint16_t
 // heads beyond 2^24 (a [tokens, 3 * heads * 128] row no allocation holds) would overflow the x grid: refused, nothing launched.
 constexpr int MAX_HEADS = 1 << 24;
 
+// The grouped-query forms (include/mxq_hip.h, "Grouped-query attention"): a qkv row is q[heads*128] | k[kv_heads*128] |
+// v[kv_heads*128], the caches hold kv_heads heads, query head h reads K/V head h / G.  The multi-head entries are the case
+// kv_heads == heads: row stride 3 * hidden, K at hidden, V at 2 * hidden, G = 1.
+int mxq_launch_kv_append_rope_gqa_f16(const void* qkv, void* k_cache, void* v_cache, const void* cos_t, const void* sin_t,
+                                      int tokens, int pos0, int heads, int kv_heads, int max_ctx, hipStream_t stream) {
+    if (heads > MAX_HEADS || kv_heads < 1 || kv_heads > heads) return (int)hipErrorInvalidValue;
+    const int64_t hidden = (int64_t)heads * HD, kv = (int64_t)kv_heads * HD;
+    kv_append_rope_kernel<<<dim3((kv_heads * 8 + 255) / 256, tokens), 256, 0, stream>>>(
+        (const uint16_t*)qkv, (uint16_t*)k_cache, (uint16_t*)v_cache, (const float*)cos_t, (const float*)sin_t, tokens, pos0, kv_heads,
+        max_ctx, hidden + 2 * kv, hidden, hidden + kv);
+    return (int)hipGetLastError();
+}
+
+int mxq_launch_attn_prefill_gqa_f16(const void* qkv, const void* k_cache, const void* v_cache, const void* cos_t, const void* sin_t,
+                                    void* out, int tokens, int pos0, int heads, int kv_heads, int max_ctx, hipStream_t stream) {
+    if (heads > MAX_HEADS || kv_heads < 1 || heads % kv_heads != 0) return (int)hipErrorInvalidValue;
+    attn_prefill_kernel<<<dim3(heads, (tokens + BQ - 1) / BQ), PF_THREADS, 0, stream>>>(
+        (const uint16_t*)qkv, (const uint16_t*)k_cache, (const uint16_t*)v_cache, (const float*)cos_t, (const float*)sin_t,
+        (uint16_t*)out, tokens, pos0, heads, max_ctx, (int64_t)(heads + 2 * kv_heads) * HD, heads / kv_heads);
+    return (int)hipGetLastError();
+}
+
 int mxq_launch_kv_append_rope_f16(const void* qkv, void* k_cache, void* v_cache, const void* cos_t, const void* sin_t, int tokens,
                                   int pos0, int heads, int max_ctx, hipStream_t stream) {
-    if (heads > MAX_HEADS) return (int)hipErrorInvalidValue;
-    kv_append_rope_kernel<<<dim3((heads * 8 + 255) / 256, tokens), 256, 0, stream>>>((const uint16_t*)qkv, (uint16_t*)k_cache,
-                                                                                     (uint16_t*)v_cache, (const float*)cos_t,
-                                                                                     (const float*)sin_t, tokens, pos0, heads, max_ctx);
-    return (int)hipGetLastError();
+    return mxq_launch_kv_append_rope_gqa_f16(qkv, k_cache, v_cache, cos_t, sin_t, tokens, pos0, heads, heads, max_ctx, stream);
 }
 
 int mxq_launch_attn_prefill_f16(const void* qkv, const void* k_cache, const void* v_cache, const void* cos_t, const void* sin_t,
                                 void* out, int tokens, int pos0, int heads, int max_ctx, hipStream_t stream) {
-    if (heads > MAX_HEADS) return (int)hipErrorInvalidValue;
-    attn_prefill_kernel<<<dim3(heads, (tokens + BQ - 1) / BQ), PF_THREADS, 0, stream>>>(
-        (const uint16_t*)qkv, (const uint16_t*)k_cache, (const uint16_t*)v_cache, (const float*)cos_t, (const float*)sin_t,
-        (uint16_t*)out, tokens, pos0, heads, max_ctx);
-    return (int)hipGetLastError();
+    return mxq_launch_attn_prefill_gqa_f16(qkv, k_cache, v_cache, cos_t, sin_t, out, tokens, pos0, heads, heads, max_ctx, stream);
 }

@@ -298,6 +298,54 @@ int mxq_attn_prefill_f16(const void* qkv, void* k_cache, void* v_cache, const vo
     return mxq_launch_attn_prefill_f16(qkv, k_cache, v_cache, cos_t, sin_t, out, tokens, pos0, heads, max_ctx, (hipStream_t)stream);
 }
 
+// grouped-query attention (csrc/attn_gqa.hip, csrc/attn_prefill.hip): heads = G * kv_heads, 1 <= G <= 16
+static bool gqa_heads_ok(int heads, int kv_heads) {
+    return heads > 0 && kv_heads > 0 && heads % kv_heads == 0 && heads / kv_heads <= 16;
+}
+
+size_t mxq_attn_gqa_workspace_bytes(int batch, int heads, int kv_heads, int splits) {
+    if (!gqa_heads_ok(heads, kv_heads)) return 0;
+    if (kv_heads == heads) return mxq_attn_batch_workspace_bytes(batch, heads, splits);
+    if (batch < 1 || batch > 256 || splits < 1 || splits > 16 || (int64_t)batch * heads > (1 << 20)) return 0;
+    return ::mxq_attn_gqa_workspace_bytes_impl(batch, heads, kv_heads, splits);
+}
+
+int mxq_attn_decode_batch_gqa_f16(const void* qkv, void* k_cache, void* v_cache, const void* pos, const void* rope_rows, void* out,
+                                  int batch, int heads, int kv_heads, int head_dim, int max_ctx, int splits, void* workspace,
+                                  void* stream) {
+    if (!qkv || !k_cache || !v_cache || !pos || !rope_rows || !out) return MXQ_E_NULL;
+    if (batch < 1 || batch > 256 || !gqa_heads_ok(heads, kv_heads) || (int64_t)batch * heads > (1 << 20) || head_dim != 128 ||
+        max_ctx <= 0 || max_ctx > 32768 || splits < 1 || splits > 16 || (splits > 1 && !workspace))
+        return MXQ_E_SHAPE;
+    if (!aligned16(qkv) || !aligned16(k_cache) || !aligned16(v_cache) || !aligned16(out) || (workspace && !aligned16(workspace)) ||
+        ((uintptr_t)pos & 7) || !aligned4(rope_rows))
+        return MXQ_E_ALIGN;
+    if (kv_heads == heads)               // the layouts coincide: the multi-head launch, bit for bit
+        return mxq_launch_attn_decode_batch_f16(qkv, k_cache, v_cache, pos, rope_rows, out, batch, heads, head_dim, max_ctx, splits,
+                                                workspace, (hipStream_t)stream);
+    return mxq_launch_attn_decode_batch_gqa_f16(qkv, k_cache, v_cache, pos, rope_rows, out, batch, heads, kv_heads, max_ctx, splits,
+                                                workspace, (hipStream_t)stream);
+}
+
+int mxq_kv_append_rope_gqa_f16(const void* qkv, void* k_cache, void* v_cache, const void* cos_t, const void* sin_t, int tokens,
+                               int pos0, int heads, int kv_heads, int head_dim, int max_ctx, void* stream) {
+    if (int e = attn_prefill_check(qkv, k_cache, v_cache, cos_t, sin_t, nullptr, false, tokens, pos0, heads, head_dim, max_ctx)) return e;
+    if (!gqa_heads_ok(heads, kv_heads)) return MXQ_E_SHAPE;
+    return mxq_launch_kv_append_rope_gqa_f16(qkv, k_cache, v_cache, cos_t, sin_t, tokens, pos0, heads, kv_heads, max_ctx,
+                                             (hipStream_t)stream);
+}
+
+int mxq_attn_prefill_gqa_f16(const void* qkv, void* k_cache, void* v_cache, const void* cos_t, const void* sin_t, void* out,
+                             int tokens, int pos0, int heads, int kv_heads, int head_dim, int max_ctx, void* stream) {
+    if (int e = attn_prefill_check(qkv, k_cache, v_cache, cos_t, sin_t, out, true, tokens, pos0, heads, head_dim, max_ctx)) return e;
+    if (!gqa_heads_ok(heads, kv_heads)) return MXQ_E_SHAPE;
+    if (int e = mxq_launch_kv_append_rope_gqa_f16(qkv, k_cache, v_cache, cos_t, sin_t, tokens, pos0, heads, kv_heads, max_ctx,
+                                                  (hipStream_t)stream))
+        return e;
+    return mxq_launch_attn_prefill_gqa_f16(qkv, k_cache, v_cache, cos_t, sin_t, out, tokens, pos0, heads, kv_heads, max_ctx,
+                                           (hipStream_t)stream);
+}
+
 // int8 KV cache (csrc/attn_kv8.hip): codes 16-byte aligned, scales 4; everything else as the fp16 entries above
 static bool kv8_null(const void* kc, const void* ks, const void* vc, const void* vs) { return !kc || !ks || !vc || !vs; }
 static bool kv8_aligned(const void* kc, const void* ks, const void* vc, const void* vs) {

@@ -205,6 +205,17 @@ int mxq_launch_kv_append_rope_f16(const void* qkv, void* k_cache, void* v_cache,
                                   int pos0, int heads, int max_ctx, hipStream_t stream);
 int mxq_launch_attn_prefill_f16(const void* qkv, const void* k_cache, const void* v_cache, const void* cos_t, const void* sin_t,
                                 void* out, int tokens, int pos0, int heads, int max_ctx, hipStream_t stream);
+// the grouped-query forms of the two launches above: qkv rows q[heads*128] | k[kv_heads*128] | v[kv_heads*128], caches of
+// kv_heads heads, query head h on K/V head h / (heads / kv_heads); kv_heads == heads is the pair above
+int mxq_launch_kv_append_rope_gqa_f16(const void* qkv, void* k_cache, void* v_cache, const void* cos_t, const void* sin_t,
+                                      int tokens, int pos0, int heads, int kv_heads, int max_ctx, hipStream_t stream);
+int mxq_launch_attn_prefill_gqa_f16(const void* qkv, const void* k_cache, const void* v_cache, const void* cos_t, const void* sin_t,
+                                    void* out, int tokens, int pos0, int heads, int kv_heads, int max_ctx, hipStream_t stream);
+// csrc/attn_gqa.hip: the batched decode step with grouped K/V heads on MFMA (1 < heads / kv_heads <= 16)
+size_t mxq_attn_gqa_workspace_bytes_impl(int batch, int heads, int kv_heads, int splits);
+int mxq_launch_attn_decode_batch_gqa_f16(const void* qkv, void* k_cache, void* v_cache, const void* pos, const void* rope_rows,
+                                         void* out, int batch, int heads, int kv_heads, int max_ctx, int splits, void* ws,
+                                         hipStream_t stream);
 // csrc/attn_kv8.hip: the int8 KV cache (include/mxq_hip.h) -- batched decode over codes and scales, the quantising append of a
 // prompt's rows, the expansion of rows [0, rows) of every head into an fp16 cache
 int mxq_launch_attn_decode_batch_kv8_f16(const void* qkv, void* k_codes, void* k_scale, void* v_codes, void* v_scale, const void* pos,

@@ -52,12 +52,28 @@ class ContextWindow:
         self.pos = 0
 
 
+def _check_kv_heads(heads: int, kv_heads: Optional[int]) -> int:
+    """The K/V head count of a stage with ``heads`` query heads: None = heads; groups of 1 .. 16 query heads per K/V head."""
+    kv = heads if kv_heads is None else int(kv_heads)
+    if kv < 1 or heads % kv != 0:
+        raise ValueError(f"kv_heads must divide heads: heads {heads}, kv_heads {kv_heads!r}")
+    if heads // kv > 16:
+        raise ValueError(f"at most 16 query heads per K/V head (the MFMA's columns): heads {heads}, kv_heads {kv}")
+    return kv
+
+
 class DecodeStage:
     SPLIT_KEYS = 128          # csrc/decode_ops.hip SPLIT_MIN: contexts up to this many keys are one workgroup per head
 
     def __init__(self, layers, dev, max_ctx: int = 512, hidden: int = LS.HIDDEN, inter: int = LS.INTERMEDIATE,
                  heads: int = 32, first: bool = True, last: bool = True, vocab: int = 32000, fused: bool = True,
-                 compact: bool = False, staging: str = "swiglu", arena: bool = True):
+                 compact: bool = False, staging: str = "swiglu", arena: bool = True, kv_heads: Optional[int] = None):
+        # kv_heads (include/mxq_hip.h, "Grouped-query attention"): None = heads.  The fused single-sequence launches of this class
+        # are multi-head; a grouped stage is a BatchedDecodeStage, which passes _gqa_ok
+        self.kv_heads = _check_kv_heads(heads, kv_heads)
+        if self.kv_heads != heads and not getattr(self, "_gqa_ok", False):
+            raise ValueError(f"DecodeStage has no grouped-query attention (kv_heads {self.kv_heads} != heads {heads}): its fused "
+                             "single-sequence launches are multi-head; BatchedDecodeStage(batch=1) is the single-sequence GQA path")
         self.layers, self.dev, self.max_ctx = list(layers), dev, max_ctx
         self.hidden, self.inter, self.heads, self.hd = hidden, inter, heads, hidden // heads
         self.first, self.last, self.compact = first, last, compact
@@ -78,7 +94,8 @@ class DecodeStage:
                 g = torch.Generator(device=dev).manual_seed(1000 * li + idx)
                 W = (torch.randn(N, K, generator=g, device=dev) * 0.02).half()
                 return packing.quantize_pack(W, compact_meta=compact)     # compact: fp16 zero-points, 3.75 bit/weight
-            qkv = _concat_packed([mk(0, hidden, hidden), mk(1, hidden, hidden), mk(2, hidden, hidden)])
+            kv = self.kv_heads * self.hd              # (== hidden without grouped K/V heads)
+            qkv = _concat_packed([mk(0, hidden, hidden), mk(1, kv, hidden), mk(2, kv, hidden)])
             o = mk(3, hidden, hidden)
             gu = _concat_packed([mk(4, inter, hidden), mk(5, inter, hidden)])
             down = mk(6, hidden, inter)
@@ -119,7 +136,7 @@ class DecodeStage:
         self._h_out = torch.zeros(1, hidden, device=dev, dtype=torch.float16)
 
     def _cache_shape(self, n_layers: int):
-        return (n_layers, self.heads, self.max_ctx, self.hd)
+        return (n_layers, self.kv_heads, self.max_ctx, self.hd)
 
     def _alloc_caches(self, n_layers: int):
         self.k_cache = torch.zeros(self._cache_shape(n_layers), device=self.dev, dtype=torch.float16)
@@ -521,14 +538,24 @@ class BatchedDecodeStage(DecodeStage):
     ``k_scale`` / ``v_scale`` f32 [layers, batch, heads, max_ctx]; there is no ``k_cache`` / ``v_cache``.  A step's attention is
     mxq_attn_decode_batch_kv8_f16, a prompt's mxq_attn_prefill_kv8_f16 over ONE pair of fp16 scratch caches [heads, max_ctx,
     128] shared by all layers and slots (a prompt pass expands the slot's rows into it layer by layer).  16 (the default):
-    the fp16 caches above."""
+    the fp16 caches above.
+
+    ``kv_heads`` (None = ``heads``): grouped-query attention (include/mxq_hip.h, "Grouped-query attention") -- ``heads`` query
+    heads over ``kv_heads`` K/V heads, query head h on K/V head h // (heads // kv_heads) as HF's repeat_kv; at most 16 query
+    heads per K/V head.  q|k|v is [hidden + 2 * kv_heads * 128, hidden], the caches [layers, batch, kv_heads, max_ctx, 128]; a
+    step's attention is mxq_attn_decode_batch_gqa_f16 (which IS mxq_attn_decode_batch_f16's launch when kv_heads == heads), a
+    prompt's mxq_attn_prefill_gqa_f16.  fp16 caches only: with ``kv_bits=8`` a grouped stage is a ValueError."""
 
     def __init__(self, layers, dev, batch: int, max_ctx: int = 512, hidden: int = LS.HIDDEN, inter: int = LS.INTERMEDIATE,
                  heads: int = 32, first: bool = True, last: bool = True, vocab: int = 32000, arena: bool = True,
-                 weights_of: Optional[DecodeStage] = None, kv_bits: int = 16):
+                 weights_of: Optional[DecodeStage] = None, kv_bits: int = 16, kv_heads: Optional[int] = None):
         if kv_bits not in (16, 8):
             raise ValueError(f"kv_bits must be 16 (fp16 caches) or 8 (int8 codes + f32 row scales), got {kv_bits!r}")
         self.kv_bits = int(kv_bits)
+        kv = _check_kv_heads(heads, kv_heads)
+        if kv != heads and self.kv_bits == 8:
+            raise ValueError(f"kv_heads {kv} != heads {heads} with kv_bits=8: there is no int8 grouped-query attention kernel")
+        self._gqa_ok = True
         if hidden != heads * 128:
             raise ValueError(f"BatchedDecodeStage needs head dim 128, got {hidden} / {heads}")
         if hidden % 8 or inter % 8:
@@ -537,10 +564,11 @@ class BatchedDecodeStage(DecodeStage):
         self.batch = int(batch)
         # weights_of: share the packed weights of a stage over the same layers and sizes (built once, e.g. to compare the two)
         if weights_of is not None and (list(weights_of.layers) != list(layers) or weights_of.compact or
-                                       (weights_of.hidden, weights_of.inter) != (hidden, inter)):
-            raise ValueError("weights_of must be a stage over the same layers and sizes, with exact metadata")
+                                       (weights_of.hidden, weights_of.inter) != (hidden, inter) or
+                                       (weights_of.heads, weights_of.kv_heads) != (heads, kv)):
+            raise ValueError("weights_of must be a stage over the same layers and sizes (kv_heads included), with exact metadata")
         super().__init__(layers if weights_of is None else (), dev, max_ctx=max_ctx, hidden=hidden, inter=inter, heads=heads,
-                         first=first, last=last, vocab=vocab, fused=True, arena=arena)
+                         first=first, last=last, vocab=vocab, fused=True, arena=arena, kv_heads=kv)
         if weights_of is not None:
             self.layers, self.w = list(weights_of.layers), weights_of.w
             self._alloc_caches(len(self.layers))
@@ -548,7 +576,7 @@ class BatchedDecodeStage(DecodeStage):
         self.pos = torch.full((batch,), -1, dtype=torch.int64, device=dev)
         self.rope_rows = torch.zeros(batch, 2 * (self.hd // 2), dtype=torch.float32, device=dev)
         self.launches_per_layer = 10                                   # the eight above and the two residual adds
-        self._attn_ws = (torch.zeros(_lib.load().mxq_attn_batch_workspace_bytes(batch, heads, self.attn_splits), dtype=torch.uint8,
+        self._attn_ws = (torch.zeros(_lib.load().mxq_attn_gqa_workspace_bytes(batch, heads, kv, self.attn_splits), dtype=torch.uint8,
                                      device=dev) if self.attn_splits > 1 else None)
         self._h_in = torch.zeros(batch, hidden, device=dev, dtype=torch.float16)
         self._h_out = None
@@ -562,7 +590,7 @@ class BatchedDecodeStage(DecodeStage):
         self.sampling = [_sampling.GREEDY] * batch
 
     def _cache_shape(self, n_layers: int):
-        return (n_layers, self.batch, self.heads, self.max_ctx, self.hd)
+        return (n_layers, self.batch, self.kv_heads, self.max_ctx, self.hd)
 
     def _alloc_caches(self, n_layers: int):
         if self.kv_bits == 16:
@@ -672,9 +700,11 @@ class BatchedDecodeStage(DecodeStage):
                                                              self.heads, self.hd, self.max_ctx, splits, ws, self._st()),
                            "mxq_attn_decode_batch_kv8_f16")
             else:
-                _lib.check(lib.mxq_attn_decode_batch_f16(y.data_ptr(), self.k_cache[i].data_ptr(), self.v_cache[i].data_ptr(),
-                                                         self.pos.data_ptr(), self.rope_rows.data_ptr(), a.data_ptr(), B, self.heads,
-                                                         self.hd, self.max_ctx, splits, ws, self._st()), "mxq_attn_decode_batch_f16")
+                # (kv_heads == heads: the entry forwards to mxq_attn_decode_batch_f16's launch, bit for bit)
+                _lib.check(lib.mxq_attn_decode_batch_gqa_f16(y.data_ptr(), self.k_cache[i].data_ptr(), self.v_cache[i].data_ptr(),
+                                                             self.pos.data_ptr(), self.rope_rows.data_ptr(), a.data_ptr(), B,
+                                                             self.heads, self.kv_heads, self.hd, self.max_ctx, splits, ws, self._st()),
+                           "mxq_attn_decode_batch_gqa_f16")
             h = h + packing.linear(a, o)
             g = packing.linear(self._rms_rows(h), gu)
             act = torch.empty((B, self.inter), dtype=torch.float16, device=self.dev)
@@ -713,7 +743,9 @@ class BatchedDecodeStage(DecodeStage):
 
     def _prefill_attn(self, lib, y, k_cache, v_cache, a, T: int, p0: int, st):
         if self.kv_bits == 16:
-            return super()._prefill_attn(lib, y, k_cache, v_cache, a, T, p0, st)
+            return _lib.check(lib.mxq_attn_prefill_gqa_f16(y.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), self.cos.data_ptr(),
+                                                           self.sin.data_ptr(), a.data_ptr(), T, p0, self.heads, self.kv_heads, self.hd,
+                                                           self.max_ctx, st), "mxq_attn_prefill_gqa_f16")
         (kc, ks), (vc, vs) = k_cache, v_cache
         _lib.check(lib.mxq_attn_prefill_kv8_f16(y.data_ptr(), kc.data_ptr(), ks.data_ptr(), vc.data_ptr(), vs.data_ptr(),
                                                 self.cos.data_ptr(), self.sin.data_ptr(), a.data_ptr(), self._k_scratch.data_ptr(),

@@ -30,3 +30,11 @@ def layer_range(rank: int, world: int, n_layers: int = N_LAYERS):
 
 def linear_flops(M: int, layers: int = N_LAYERS) -> float:
     return 2.0 * M * PARAMS_PER_LAYER * layers
+
+
+# Llama-3-8B (grouped-query attention: 32 query heads over 8 key/value heads of dim 128), for tools/attn_gqa_bench.py and
+# tools/decode_batch_bench.py --kv-heads: q|k|v is [4096 + 2 * 1024, 4096], gate|up [2 * 14336, 4096], down [4096, 14336]
+L3_8B_HIDDEN = 4096
+L3_8B_INTERMEDIATE = 14336
+L3_8B_HEADS = 32
+L3_8B_KV_HEADS = 8

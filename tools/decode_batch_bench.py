@@ -12,7 +12,11 @@ and start position; then the time of a 512-token prefill_slot in both modes (the
 against the greedy one -- two batched stages on the same packed weights, alternating, same replay counts and repeats; then
 mxq_sample_rows_f16 alone at V = 32000 and B = 1 / 8 / 32 / 256 against the torch chain (softmax, topk, sort, cumsum,
 multinomial) and against the three launches it replaces in the loop (argmax, where, copy), HIP events around CALLS calls.
-    python tools/decode_batch_bench.py --sample [--out profiles/sample_bench.txt] [--batches 1,8,32]"""
+    python tools/decode_batch_bench.py --sample [--out profiles/sample_bench.txt] [--batches 1,8,32]
+--kv-heads N: grouped-query attention (BatchedDecodeStage(kv_heads=N): 32 query heads over N K/V heads) against the multi-head
+stage of the same widths -- the two captured batched token loops, each on its own packed weights (the q|k|v Linear differs),
+alternating, same replay counts and repeats; tokens/s of both, their ratio and the KV cache sizes per B and start position.
+    python tools/decode_batch_bench.py --kv-heads 8 [--out profiles/decode_gqa_bench.txt] [--batches 1,8,32]"""
 import argparse
 import os
 import sys
@@ -98,6 +102,54 @@ def kv8_main(args, dev, say):
                     f"(min {t[0]:.3f}, max {t[-1]:.3f}; {PREFILL_RUNS} runs after a warm-up one"
                     + ("; append + expand K + expand V + attention per layer)" if bits == 8 else "; append + attention per layer)"))
         del stages, bufs
+        torch.cuda.empty_cache()
+
+
+def gqa_main(args, dev, say):
+    """Multi-head against grouped-query attention: the two batched token loops per B and start position."""
+    batches, starts = [int(b) for b in args.batches.split(",")], [int(s) for s in args.starts.split(",")]
+    heads = 32
+    owners = {}
+    say(f"decode_gqa_bench: {args.layers} layers, hidden 4096, intermediate 11008, {heads} query heads, W2/4A16 mixed layout, KV cache "
+        f"{MAX_CTX} fp16; {heads} K/V heads (multi-head) against {args.kv_heads} (grouped-query, q|k|v N = {4096 + 2 * args.kv_heads * 128}); "
+        f"{TOKENS} timed graph replays after {WARM} warm-up ones, {REPEATS} repeats, the two loops alternating")
+    say(f"device: {torch.cuda.get_device_name(0)}")
+    for B in batches:
+        stages = {}
+        for kv in (heads, args.kv_heads):
+            stages[kv] = BatchedDecodeStage(range(args.layers), dev, batch=B, max_ctx=MAX_CTX, heads=heads, kv_heads=kv,
+                                            weights_of=owners.get(kv))
+            owners.setdefault(kv, stages[kv])          # the first stage of each kind owns the packed weights of the later ones
+        bufs = {kv: torch.zeros(B, dtype=torch.int64, device=dev) for kv in stages}
+        for kv, st in stages.items():
+            st.capture_token_loop(bufs[kv])
+
+        def run(kv, start, n):
+            st = stages[kv]
+            st.reset()
+            for b in range(B):
+                st.seek_slot(b, start)
+            return lambda: st.decode_tokens(bufs[kv], [1 + b for b in range(B)], n)
+
+        say(f"B {B:2d}: KV cache {stages[heads].kv_cache_bytes() / 1e9:.2f} GB multi-head, {stages[args.kv_heads].kv_cache_bytes() / 1e9:.2f} GB "
+            f"at {args.kv_heads} K/V heads; packed weights {stages[heads].packed_bytes() / 1e9:.3f} / {stages[args.kv_heads].packed_bytes() / 1e9:.3f} GB")
+        for start in starts:
+            for kv in stages:
+                run(kv, start, WARM)()
+            ratios, rows = [], []
+            for _ in range(REPEATS):
+                msm = timed(run(heads, start, TOKENS))
+                msg = timed(run(args.kv_heads, start, TOKENS))
+                ratios.append(msm / msg)
+                rows.append((msm, msg))
+            mean = sum(ratios) / len(ratios)
+            spread = (max(ratios) - min(ratios)) / mean
+            for r, (msm, msg) in enumerate(rows):
+                say(f"B {B:2d} start {start:4d} repeat {r}: multi-head {B / msm * 1e3:8.1f} tokens/s aggregate, {msm:7.3f} ms/step; "
+                    f"{args.kv_heads} K/V heads {B / msg * 1e3:8.1f} tokens/s aggregate, {msg:7.3f} ms/step; ratio {ratios[r]:.3f}")
+            say(f"B {B:2d} start {start:4d}: grouped-query tokens/s over multi-head tokens/s {mean:.3f} (spread of the {REPEATS} repeats "
+                f"{spread * 100:.1f} %)")
+        del stages, bufs                               # (the owners stay alive for their weights; their caches are B_0's)
         torch.cuda.empty_cache()
 
 
@@ -222,15 +274,17 @@ def main():
                     help="8: compare the int8 KV cache's batched loop with the fp16 one (profiles/decode_kv8_bench.txt)")
     ap.add_argument("--sample", action="store_true",
                     help="compare the sampled captured loop with the greedy one, and time the sampler alone (profiles/sample_bench.txt)")
+    ap.add_argument("--kv-heads", type=int, default=None,
+                    help="compare a grouped-query stage (32 query heads over this many K/V heads) with the multi-head one (profiles/decode_gqa_bench.txt)")
     ap.add_argument("--sampled-first", action="store_true", help="with --sample: allocate and capture the sampled stage first")
     ap.add_argument("--no-per-call", action="store_true", help="with --sample: skip the per-call timings")
     args = ap.parse_args()
     kv8 = args.kv_bits == 8
     if args.out is None:
         args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                "sample_bench.txt" if args.sample else "decode_kv8_bench.txt" if kv8 else "decode_batch_bench.txt")
+                                "decode_gqa_bench.txt" if args.kv_heads else "sample_bench.txt" if args.sample else "decode_kv8_bench.txt" if kv8 else "decode_batch_bench.txt")
     if args.batches is None:
-        args.batches = "1,8,32" if args.sample else "1,8,16,32" if kv8 else "1,2,4,8,16,32"
+        args.batches = "1,8,32" if (args.sample or args.kv_heads) else "1,8,16,32" if kv8 else "1,2,4,8,16,32"
     dev = torch.device("cuda:0")
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     out = open(args.out, "w")
@@ -240,6 +294,10 @@ def main():
         out.write(line + "\n")
         out.flush()
 
+    if args.kv_heads:
+        gqa_main(args, dev, say)
+        out.close()
+        return
     if args.sample:
         sample_main(args, dev, say)
         out.close()
